@@ -905,6 +905,35 @@ def scaling_workload(device, rank, world, group, rounds=3):
                     "rank: no collective)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Writes every array of `arrays` as out_dir/<name>.npy in float64, DUMP_LIMIT_BYTES at most in all: the arrays are
+    taken smallest first, each kept whole when it fits an equal share of what is left of the budget, and otherwise cut to a
+    fixed, seeded sample of its rows (their indices: <name>_rows.npy), so that two runs with the same arguments write the
+    same files.  Returns the names of the files written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    budget = DUMP_LIMIT_BYTES - 256 * 2 * len(arrays)          # (.npy headers)
+    order = sorted(arrays, key=lambda name_: (arrays[name_].nbytes, name_))
+    written = []
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = budget // (len(order) - i)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0] + 8               # (+ the row's index, stored as float64)
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=max(1, share // row_bytes), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            written.append(name + "_rows.npy")
+            budget -= rows.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written.append(name + ".npy")
+        budget -= a.nbytes
+    return sorted(written)
+
+
 def headline_workload_name(world):
     """config.workload of the line: at N > 1 the headline is the WEAK-scaled metric workload (9298 rows on every GPU: a step is
     launch-latency bound there and the line prices the collective); north_star's strong-scaling curve is scaling_workload."""
@@ -1002,7 +1031,13 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch path only (no GPU): the ranks rendezvous over gloo, agree on a digest and rank 0 prints a "
                          "line with dry_run: true -- what tests/test_bench_launch.py runs on CPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): picks = the batch "
+                         "fetch_unlabelled returned, posterior_mean / posterior_var = the GP posterior of every sample after "
+                         "that step's update(); same arguments, same inputs, same files")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     globals().update(ROWS_PER_GPU=args.rows, BATCH=args.batch)
     t_process = time.perf_counter()
 
@@ -1122,6 +1157,14 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     launches_end = _lib.lib().ital_launch_count()
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: the batch fetch_unlabelled returned and the posterior
+        # that step's update() left (predict_stored is a collective when the rows are sharded: every rank calls it)
+        mean, var = learner.gp.predict_stored(cov_mode="diag")
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"picks": np.asarray(timed_picks[-1], dtype=np.float64),
+                                                      "posterior_mean": mean, "posterior_var": var})
     head_sha, head_words = picks_digest(timed_picks)
     head_agree = ranks_agree(head_words, device, world)
     head_transport = transport_report(learner, group, device)
@@ -1273,6 +1316,8 @@ def main():
                "library_launches_per_step": launches, "round_gaps": round_gaps(),
                "picks_sha": head_sha, "picks_agree_across_ranks": head_agree, **head_transport,
                "scaling_workload": scale}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
         if scale is not None:
             # the strong-scaling figure north_star asks for (1M x 512, k = 4, rows split over the ranks), also at top level
             out["value_strong_1M"] = scale["candidates_per_s"]

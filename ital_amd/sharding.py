@@ -271,14 +271,20 @@ def await_download(tensor, what, group=None, device=None, comm=None, rank=0, wor
     return host.clone() if pinned is not None else host      # (the landing buffer is reused by the next round)
 
 
+_PEEK_STREAMS = {}       # device -> the side stream of _peek
+
+
 def _peek(tensor, cache):
     """The CURRENT content of a small device buffer (bytes), read through a side stream while the buffer's own stream is busy:
     the progress probe of await_download.  None when the copy does not come back within a second (nothing is concluded)."""
     import time
     import torch
-    side = cache.get("peek_stream")
+    # a HIGH-priority stream, one per device: the runtime spreads normal-priority streams round-robin over a few hardware
+    # queues (GPU_MAX_HW_QUEUES), so a normal one made after others can share the busy stream's queue and the copy then
+    # waits behind the round's kernels -- no progress is ever seen; the high-priority queues carry nothing else
+    side = _PEEK_STREAMS.get(str(tensor.device))
     if side is None:
-        side = cache["peek_stream"] = torch.cuda.Stream(device=tensor.device)
+        side = _PEEK_STREAMS[str(tensor.device)] = torch.cuda.Stream(device=tensor.device, priority=-1)
     key = ("peek", tuple(tensor.shape), tensor.dtype)
     land = cache.get(key)
     if land is None:

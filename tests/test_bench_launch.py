@@ -52,3 +52,34 @@ def test_a_failing_rank_fails_the_parent():
 def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "4", "--dry-run"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "--gpus 4" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_limit_and_the_same_sample_every_time(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = {"picks": [5, 1, 7, 2], "posterior_mean": np.arange(100.0), "posterior_var": np.linspace(0, 1, 100)}
+    assert bench.dump_outputs(str(tmp_path / "small"), small) == ["picks.npy", "posterior_mean.npy", "posterior_var.npy"]
+    for name, a in small.items():
+        got = np.load(str(tmp_path / "small" / (name + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(a, dtype=np.float64))
+    # more than the limit: a fixed, seeded sample of the rows, the same in two runs, and the files stay under the limit
+    big = {"picks": [5, 1, 7, 2], "posterior_mean": np.arange(3 * 10 ** 5, dtype=np.float64), "posterior_var": np.ones((10 ** 5, 3))}
+    limit = bench.DUMP_LIMIT_BYTES
+    bench.DUMP_LIMIT_BYTES = 1 << 20
+    try:
+        files = [bench.dump_outputs(str(tmp_path / d), big) for d in ("a", "b")]
+    finally:
+        bench.DUMP_LIMIT_BYTES = limit
+    assert files[0] == files[1] and "posterior_mean_rows.npy" in files[0]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files[0]) <= 1 << 20
+    for f in files[0]:
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f)))
+    rows = np.load(str(tmp_path / "a" / "posterior_mean_rows.npy")).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "posterior_mean.npy")), big["posterior_mean"][rows])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "picks.npy")), [5.0, 1.0, 7.0, 2.0])
+
+
+def test_steps_below_one_is_refused():
+    r = _run(["--gpus", "1", "--steps", "0", "--dry-run"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
