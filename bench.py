@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 10 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --full ...          # + everything else this file measures (~4 minutes on one GPU)
 
 One "step" = one round of the reference's retrieval loop (run_experiment.py:160-164): fetch_unlabelled(k) on the
 current relevance model followed by update() with the simulated feedback for the fetched batch (the update is
@@ -13,9 +14,12 @@ Headline (`value`): BASELINE.json configs[1], SURVEY.md section 8d C2': syntheti
 exchange one record per rank over RCCL.  A scored candidate = one (candidate, greedy step) MI evaluation with full 2^t
 sign-pattern enumeration.
 
-Every line also carries `scaling_workload`: the curve north_star asks for -- 1 000 000 x 512, k = 4, full enumeration,
-the rows STRONG-scaled over the N ranks (each rank generates and holds only its own row block), timed the same way
-(barrier + synchronize on both sides, maximum over ranks), with the per-step record exchange priced separately.
+A plain run does only what the headline needs: set-up, pre-heat, warm-up, the timed steps, --dump-outputs, the line.
+With --full the same timed steps are followed by everything else: CPU baselines, seeds 1 and 2, per-kernel times and
+rooflines, the other BASELINE configurations and `scaling_workload`: the curve north_star asks for -- 1 000 000 x 512,
+k = 4, full enumeration, the rows STRONG-scaled over the N ranks (each rank generates and holds only its own row block),
+timed the same way (barrier + synchronize on both sides, maximum over ranks), with the per-step record exchange priced
+separately.
 """
 import argparse
 import gc
@@ -997,12 +1001,35 @@ def dry_run(rank, world, args):
         dist.destroy_process_group()
     if rank == 0:
         # (the keys a reader of an N > 1 line looks for are present in the dry run too: tests/test_bench_launch.py)
-        print(json.dumps({"metric": "MI-scored candidates/sec per fetch_unlabelled(k) round", "value": None, "dry_run": True,
-                          "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ranks_seen": ranks,
-                          "picks_agree_across_ranks": agree, "scaling": "weak",
-                          "config": {"workload": headline_workload_name(world)},
-                          "scaling_workload": {"scaling": "strong", "world_size": world, "ms_per_round": None, "n1_ms_per_round": None,
-                                               "speedup_vs_n1": None, "efficiency": None}}), flush=True)
+        line = {"metric": "MI-scored candidates/sec per fetch_unlabelled(k) round", "value": None, "dry_run": True,
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ranks_seen": ranks,
+                "picks_agree_across_ranks": agree, "scaling": "weak",
+                "config": {"workload": headline_workload_name(world)}}
+        if args.full:
+            line["scaling_workload"] = {"scaling": "strong", "world_size": world, "ms_per_round": None, "n1_ms_per_round": None,
+                                        "speedup_vs_n1": None, "efficiency": None}
+        print(json.dumps(line), flush=True)
+
+
+def emit_line(out, group, agree):
+    """Rank 0 prints `out` as the LAST thing on stdout; every rank leaves the process group; exits non-zero when the ranks
+    did not pick the same batches."""
+    # RCCL prints a version banner through C stdio, which a redirected stdout holds back until the process ends -- every
+    # rank pushes its own out before the final barrier, rank 0 prints after it
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except OSError:
+        pass
+    sys.stdout.flush()
+    if group is not None:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    if out is not None:
+        print(json.dumps(out), flush=True)
+    if not agree:
+        raise SystemExit("bench.py: the ranks did NOT pick the same batches -- the line above is not a valid measurement")
 
 
 def main():
@@ -1010,19 +1037,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else this file measures: the CPU baselines, seeds 1 and 2, the "
+                         "unfrozen-heap and fetch / update split timings, per-kernel times and rooflines, the 1M x 512 scaling "
+                         "workload and the other BASELINE configurations (~4 minutes on one GPU); the options below that skip "
+                         "or add parts of it act on a --full run only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-scaling-workload", action="store_true", help="skip the 1M x 512 strong-scaling record")
     ap.add_argument("--rows", type=int, default=9298, help="rows per GPU (experiments; the default is the metric's workload)")
     ap.add_argument("--batch", type=int, default=4, help="batch size k (experiments)")
     ap.add_argument("--label-prob", type=float, default=1.0, help="user model (experiments; != 1 selects the general scorer)")
     ap.add_argument("--mistake-prob", type=float, default=0.0)
-    ap.add_argument("--extra", default="", help="comma list of opt-in workloads (N = 1): topcand = 1 000 000 x 512 with "
-                    "top_candidates = 4096 (the host's argpartition share).  (c4 / c5k16 -- BASELINE configs[3] and [4] -- are part "
-                    "of the default run since round 6.)")
+    ap.add_argument("--extra", default="", help="comma list of opt-in workloads (N = 1, with --full): topcand = 1 000 000 x 512 "
+                    "with top_candidates = 4096 (the host's argpartition share).  (c4 / c5k16 -- BASELINE configs[3] and [4] -- are "
+                    "part of every --full run.)")
     ap.add_argument("--quick", action="store_true",
                     help="headline + scaling workload only: skips the other BASELINE configurations (configs[2], [3], [4] share "
-                         "and whole, the noisy user, MCMI, the 20 000^2 covariance block) and their CPU baselines, which the "
-                         "default run times in ~4 minutes (ITAL_BENCH_NO_EXTRAS=1 does the same)")
+                         "and whole, the noisy user, MCMI, the 20 000^2 covariance block) and their CPU baselines, which a "
+                         "--full run times in ~4 minutes (ITAL_BENCH_NO_EXTRAS=1 does the same)")
     ap.add_argument("--no-c5-whole", action="store_true",
                     help="skip BASELINE configs[4] in one piece (1 000 000 x 512, k = 16: ~90 s of GPU); its 125 000-row share "
                          "(what one of 8 ranks runs) stays")
@@ -1038,6 +1070,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.extra and not args.full:
+        ap.error("--extra adds workloads to a --full run: give --full too")
     globals().update(ROWS_PER_GPU=args.rows, BATCH=args.batch)
     t_process = time.perf_counter()
 
@@ -1052,8 +1086,8 @@ def main():
         return dry_run(rank, world, args)
     cpu_base = None
     cpu_other = {}
-    extras_on = world == 1 and not args.quick and not os.environ.get("ITAL_BENCH_NO_EXTRAS")
-    if world == 1 and not args.no_cpu_baseline:
+    extras_on = args.full and world == 1 and not args.quick and not os.environ.get("ITAL_BENCH_NO_EXTRAS")
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # before anything touches the GPU: the baselines fork worker pools
         cores = cpu_cores()
         cpu_base = cpu_baseline(make_data(ROWS_PER_GPU, DIM, seed=0), cores)
@@ -1138,6 +1172,7 @@ def main():
     for _ in range(args.warmup):
         one_round()
     restart()
+    # (a plain run records the events too and never reads them: its timed steps stay those of a --full run)
     learner.profile = [] if use_events else None
     learner.profile_steps = {BATCH}      # events around the dominant kernel only (every record is a barrier packet in the queue)
     learner.event_pool = pool
@@ -1168,6 +1203,27 @@ def main():
     head_sha, head_words = picks_digest(timed_picks)
     head_agree = ranks_agree(head_words, device, world)
     head_transport = transport_report(learner, group, device)
+    launches = (launches_end - launches0) / args.steps
+    if os.environ.get("ITAL_BENCH_STEP_TIMES"):
+        print("step ms (timed):    " + " ".join("%.2f" % ((b_ - a_) * 1e3) for a_, b_ in zip([t0] + marks[:-1], marks)), file=sys.stderr)
+    dt = max(gather_floats(dt, device, world))
+    out = None
+    if rank == 0:
+        out = {"metric": "MI-scored candidates/sec per fetch_unlabelled(k) round", "value": scored / dt,
+               "unit": "candidates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+               "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+               "config": {"workload": headline_workload_name(world),
+                          "n": n_total, "d": DIM, "k": BATCH, "length_scale": LENGTH_SCALE,
+                          "parallelism": "candidate rows sharded over %d GPU(s), 1 record all-gather per greedy step" % world},
+               "fit_ms": fit_ms, "library_launches_per_step": launches,
+               "picks_sha": head_sha, "picks_agree_across_ranks": head_agree, **head_transport}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
+    if not args.full:
+        return emit_line(out, group, head_agree)
+
+    # ---- --full: everything else, after the timed steps
     # the same K steps with the interpreter's heap as a process that never froze it has it (reported next to the headline)
     prof_timed, learner.profile = learner.profile, None
     gc.unfreeze()
@@ -1183,14 +1239,8 @@ def main():
     parts = split_rounds(learner, lambda i: float(rel[i]), BATCH, min(args.steps, 5), barrier)
     learner.profile = prof_timed
     if os.environ.get("ITAL_BENCH_STEP_TIMES"):
-        print("step ms (timed):    " + " ".join("%.2f" % ((b_ - a_) * 1e3) for a_, b_ in zip([t0] + marks[:-1], marks)), file=sys.stderr)
         print("step ms (unfrozen): " + " ".join("%.2f" % ((b_ - a_) * 1e3) for a_, b_ in zip([tu] + marks_u[:-1], marks_u)), file=sys.stderr)
-    launches = (launches_end - launches0) / args.steps
-    if world > 1:
-        import torch.distributed as dist
-        tt = torch.tensor([dt, dt_unfrozen], dtype=torch.float64, device=device)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt, dt_unfrozen = float(tt[0].item()), float(tt[1].item())
+    dt_unfrozen = max(gather_floats(dt_unfrozen, device, world))
 
     # per-kernel durations from the HIP events recorded on the launch stream during the timed region (the lattice sums: the
     # library brackets them itself); the short kernels of the first greedy steps are sampled in three more rounds, untimed,
@@ -1259,7 +1309,6 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
         scale = scaling_workload(device, rank, world, group)
-    out = None
     if rank == 0:
         qm = prof.get(("qmc_main", BATCH), [])
         roof = None
@@ -1300,24 +1349,13 @@ def main():
         if scale is not None:
             strong = {k_: scale[k_] for k_ in ("ms_per_round", "candidates_per_s", "n1_ms_per_round", "speedup_vs_n1", "efficiency",
                                                "world_size", "picks_match_n1")}
-        out = {"metric": "MI-scored candidates/sec per fetch_unlabelled(k) round", "value": scored / dt,
-               "unit": "candidates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": headline_workload_name(world),
-                          "n": n_total, "d": DIM, "k": BATCH, "length_scale": LENGTH_SCALE,
-                          "parallelism": "candidate rows sharded over %d GPU(s), 1 record all-gather per greedy step" % world,
-                          "seeds": seeds_obj, "strong_scaling_1M": strong},
-               "roofline_hbm_at_workload_size": roof_hbm,
-               "kernel_ms": {"%s_t%d" % k: float(np.mean([d for d, _ in v])) * 1e3 for k, v in sorted(prof.items())},
-               "fit_ms": fit_ms, "fetch_ms_per_round": parts["fetch_ms_per_round"], "update_ms_per_round": parts["update_ms_per_round"],
-               "fetch_update_split_note": parts["note"],
-               "ms_per_step_unfrozen_heap": dt_unfrozen / args.steps * 1e3, "preheat_rounds_before_warmup": preheat,
-               "library_launches_per_step": launches, "round_gaps": round_gaps(),
-               "picks_sha": head_sha, "picks_agree_across_ranks": head_agree, **head_transport,
-               "scaling_workload": scale}
-        if dumped is not None:
-            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
+        out["config"].update(seeds=seeds_obj, strong_scaling_1M=strong)
+        out.update({"roofline_hbm_at_workload_size": roof_hbm,
+                    "kernel_ms": {"%s_t%d" % k: float(np.mean([d for d, _ in v])) * 1e3 for k, v in sorted(prof.items())},
+                    "fetch_ms_per_round": parts["fetch_ms_per_round"], "update_ms_per_round": parts["update_ms_per_round"],
+                    "fetch_update_split_note": parts["note"],
+                    "ms_per_step_unfrozen_heap": dt_unfrozen / args.steps * 1e3, "preheat_rounds_before_warmup": preheat,
+                    "round_gaps": round_gaps(), "scaling_workload": scale})
         if scale is not None:
             # the strong-scaling figure north_star asks for (1M x 512, k = 4, rows split over the ranks), also at top level
             out["value_strong_1M"] = scale["candidates_per_s"]
@@ -1400,22 +1438,7 @@ def main():
                                       "cpu_baseline_candidates_per_s (extrapolated beyond C2')"], "rows": summ,
                           "ms_per_step_seeds_0_1_2": [round(seed_ms[q], 3) for q in sorted(seed_ms)], "cpu_cores": cpu_base and cpu_base["cores"],
                           "bench_wall_s": round(time.perf_counter() - t_process, 1)}
-    # the JSON line is the LAST thing on stdout: RCCL prints a version banner through C stdio, which a redirected stdout holds
-    # back until the process ends -- every rank pushes its own out before the final barrier, rank 0 prints after it
-    try:
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-    except OSError:
-        pass
-    sys.stdout.flush()
-    if group is not None:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
-    if out is not None:
-        print(json.dumps(out), flush=True)
-    if not head_agree or (scale is not None and not scale["picks_agree_across_ranks"]):
-        raise SystemExit("bench.py: the ranks did NOT pick the same batches -- the line above is not a valid measurement")
+    emit_line(out, group, head_agree and (scale is None or scale["picks_agree_across_ranks"]))
 
 
 if __name__ == "__main__":

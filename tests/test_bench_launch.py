@@ -19,7 +19,7 @@ def _run(argv, env_extra=None, timeout=300):
 
 
 def test_gpus_2_without_a_launcher_starts_two_ranks():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"])
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     line = json.loads(lines[-1])                     # the JSON line is the LAST thing on the parent's stdout
@@ -33,6 +33,16 @@ def test_gpus_2_without_a_launcher_starts_two_ranks():
     sw = line["scaling_workload"]
     assert sw["scaling"] == "strong" and sw["world_size"] == 2
     assert {"ms_per_round", "n1_ms_per_round", "speedup_vs_n1", "efficiency"} <= set(sw)
+
+
+def test_a_plain_run_leaves_the_full_parts_out():
+    # without --full the line carries the headline only; --extra asks for more work than that and needs --full
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and "scaling_workload" not in line
+    r = _run(["--gpus", "1", "--dry-run", "--extra", "topcand"])
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def test_one_rank_line_names_the_headline_workload_plainly():

@@ -8,7 +8,7 @@ cd $ROOT
 ( nproc; cat /sys/fs/cgroup/cpu.max 2>/dev/null; python3 -c "import os; print('affinity', len(os.sched_getaffinity(0)), 'cpu_count', os.cpu_count())"; free -g | head -2 ) > $OUT/box.txt 2>&1
 timeout 1500 python3 -m pytest tests -m gpu -x -q > $OUT/gputests.log 2>&1
 echo "pytest rc $?" >> $OUT/gputests.log
-ITAL_BENCH_WRITE_PICKS=$OUT/scaling_picks_n1.json timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+ITAL_BENCH_WRITE_PICKS=$OUT/scaling_picks_n1.json timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench rc $?" >> $OUT/bench_default.err
 LIMIT=${FUZZ_LIMIT:-700}
 run() {  # kinds seed cases maxd

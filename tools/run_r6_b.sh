@@ -12,8 +12,8 @@ for c in 12 133; do
   ITAL_HIP_LIB=$ROOT/build_variants/libital_r5.so FUZZ_KINDS=optclip FUZZ_MAX_D=3 timeout 300 python3 tools/fuzz_parity.py 450 317 $c 2>&1 | grep -v "cand \|^round" | tail -n 3 > $OUT/old_optclip_317_case$c.log
   FUZZ_KINDS=optclip FUZZ_MAX_D=3 timeout 300 python3 tools/fuzz_parity.py 450 317 $c 2>&1 | grep -v "cand \|^round" | tail -n 3 > $OUT/new_optclip_317_case$c.log
 done
-timeout 300 python3 bench.py --quick --label-prob 0.5 --mistake-prob 0.25 --no-cpu-baseline --no-scaling-workload --steps 6 --warmup 2 > $OUT/bench_noisy.json 2> $OUT/bench_noisy.err
-ITAL_HIP_LIB=$ROOT/build_variants/libital_r5.so timeout 300 python3 bench.py --quick --label-prob 0.5 --mistake-prob 0.25 --no-cpu-baseline --no-scaling-workload --steps 6 --warmup 2 > $OUT/bench_noisy_r5lib.json 2> $OUT/bench_noisy_r5lib.err
+timeout 300 python3 bench.py --full --quick --label-prob 0.5 --mistake-prob 0.25 --no-cpu-baseline --no-scaling-workload --steps 6 --warmup 2 > $OUT/bench_noisy.json 2> $OUT/bench_noisy.err
+ITAL_HIP_LIB=$ROOT/build_variants/libital_r5.so timeout 300 python3 bench.py --full --quick --label-prob 0.5 --mistake-prob 0.25 --no-cpu-baseline --no-scaling-workload --steps 6 --warmup 2 > $OUT/bench_noisy_r5lib.json 2> $OUT/bench_noisy_r5lib.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/general_stats -o stats -- python3 $ROOT/bench.py --quick --label-prob 0.5 --mistake-prob 0.25 --no-cpu-baseline --no-scaling-workload --steps 3 --warmup 1 > $OUT/general_stats.log 2>&1
 cp $(find $OUT/general_stats -name "*kernel_stats.csv" | head -1) $OUT/r6_general_kernel_stats.csv

@@ -11,7 +11,7 @@ bash tools/profile_r6.sh headline k8 general c5 mcmi kcols > $OUT/profile.log 2>
 cp $ROOT/gpurun_out/prof_r6/r6_* $ROOT/profiles/ 2>/dev/null
 python3 tools/stamp.py --check profiles/r6_stamp.json > $OUT/stamp_check.txt 2>&1
 cd $ROOT
-timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench rc $?" >> $OUT/bench_default.err
 tail -n 6 $OUT/gputests_exchange.log
 tail -n 12 $OUT/profile.log

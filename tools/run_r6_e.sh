@@ -7,9 +7,9 @@ mkdir -p $OUT
 cd $ROOT
 timeout 1800 python3 -m pytest tests -m gpu -q > $OUT/gputests.log 2>&1
 echo "pytest rc $?" >> $OUT/gputests.log
-ITAL_BENCH_ONE_DEVICE=1 ITAL_BENCH_BACKEND=gloo timeout 900 python3 bench.py --gpus 2 --steps 5 --warmup 2 > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err
+ITAL_BENCH_ONE_DEVICE=1 ITAL_BENCH_BACKEND=gloo timeout 900 python3 bench.py --full --gpus 2 --steps 5 --warmup 2 > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err
 echo "bench2 rc $?" >> $OUT/bench_2rank_gloo.err
-timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench rc $?" >> $OUT/bench_default.err
 tail -n 6 $OUT/gputests.log
 tail -n 3 $OUT/bench_2rank_gloo.err
