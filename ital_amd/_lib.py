@@ -1,4 +1,4 @@
-"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h).
+"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h and include/ital_ctx.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -161,6 +161,22 @@ SIGNATURES = {
 }
 
 
+class ItalCtxModel(ctypes.Structure):
+    """ital_ctx_model (include/ital_ctx.h): the user model of a context."""
+    _fields_ = [("label_prob", c_double), ("mistake_prob", c_double), ("label_estimation", c_int),
+                ("monte_carlo_num_rel", c_int), ("monte_carlo_num_fb", c_int), ("clip_cov", c_double)]
+
+
+#: the context layer beyond the perfect user, declared in include/ital_ctx.h (SIGNATURES mirrors include/ital_hip.h alone)
+CTX_SIGNATURES = {
+    "ital_ctx_set_model": (c_int, [c_void_p, ctypes.POINTER(ItalCtxModel)]),
+    "ital_ctx_fetch_list": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "ital_ctx_mcmi_fetch": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ital_ctx_top_results": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "ital_ctx_predict": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -179,8 +195,8 @@ def load(path=LIB_PATH):
     except ImportError:
         pass
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
+    for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()):
+        fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args
     return lib

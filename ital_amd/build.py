@@ -30,7 +30,7 @@ def _newer(target, deps):
 
 def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-              [os.path.join(INCLUDE, "ital_hip.h")]
+              [os.path.join(INCLUDE, "ital_hip.h"), os.path.join(INCLUDE, "ital_ctx.h")]
     objdir = os.environ.get("ITAL_OBJ_DIR", os.path.join(HERE, "_obj"))
     os.makedirs(objdir, exist_ok=True)
     jobs = []
