@@ -1,4 +1,4 @@
-"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h and include/ital_ctx.h).
+"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h and include/ital_dense.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -177,6 +177,18 @@ CTX_SIGNATURES = {
 }
 
 
+#: the dense kernels of the hyper-parameter search, declared in include/ital_dense.h
+DENSE_SIGNATURES = {
+    "ital_gram_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
+                               c_double, c_double, c_void_p]),
+    "ital_chol_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ital_chol_solve_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "ital_kernel_matvec": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
+                                   c_double, c_double, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "ital_kernel_matvec_workspace": (c_int64, [c_int64, c_int64]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -195,7 +207,7 @@ def load(path=LIB_PATH):
     except ImportError:
         pass
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args
