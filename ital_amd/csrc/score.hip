@@ -28,6 +28,7 @@
 #include "qmc_common.h"
 #include "qmc_exact.h"
 #include "qmc_seed.h"
+#include "qmc_share.h"
 #include "select_common.h"
 
 #ifndef ITAL_QMC_HOTK
@@ -79,6 +80,29 @@
 #endif
 #ifndef ITAL_QMC_MAIN_CFL
 #define ITAL_QMC_MAIN_CFL(T) ((T) >= 7)  // ... with the factor read from LDS at use instead of held in scalar registers
+#endif
+
+#ifndef ITAL_QMC_SHARE_LAST
+// The 16 chains that the three six-chain rounds of a t = 4 lattice sum leave over are evaluated for four records in one
+// round (qmc_share.h, qmc_main_shared below) instead of as a fourth round of one chain per lane, 48 of 64 lanes idle, for
+// every record: a wave takes four consecutive sign patterns of a candidate.  0: one record per wave, every wave runs its own
+// left-over round (qmc_lane_sum).  Applies where Qmc<T>::SHARE holds: of the instantiated dimensions only T = 4; every other
+// T compiles to the same code either way.  Same sums bit for bit.
+// Measured (9298 x 256, k = 4, same box, profiles/share_last_*): qmc_main_kernel<4> 1.737 -> 1.669 ms, vector instructions
+// per launch 9.39e8 -> 8.65e8 (-7.8 %), scalar 4.33e8 -> 3.83e8; the round 2.373 -> 2.310 ms.
+// The form first tried -- one record per wave, the four waves of a workgroup handing their left-over chains to the wave that
+// finishes last (LDS, a ticket, no barrier) -- removed as many instructions and was SLOWER, 1.746 -> 1.813 ms: the wave
+// slots of the three waves that retire early are not refilled before the workgroup ends (resident wave-cycles -28 %).
+#define ITAL_QMC_SHARE_LAST 1
+#endif
+#ifndef ITAL_QMC_SHARE_RECS
+#define ITAL_QMC_SHARE_RECS 4   // records per wave where the left-over chains are shared (4 x 16 chains: a full wave)
+#endif
+#ifndef ITAL_QMC_SHARE_VCF
+// ... with the last ITAL_QMC_SHARE_VCF values of the factor as vector values: the scalar file is full inside the lattice sum
+// and the compiler keeps all six values in lane spills otherwise (105 lane reads and writes per record loop trip; 63 with
+// three, 1.694 -> 1.669 ms; four or more spill vector registers to scratch)
+#define ITAL_QMC_SHARE_VCF 3
 #endif
 
 namespace ital {
@@ -220,6 +244,7 @@ __global__ __launch_bounds__(256) void score_t2_kernel(ScoreArgs a) {
 //   qmc_prep_kernel<T> thread per (candidate, r)    candidate-level algebra, the standardised prior problem of sign pattern r,
 //                                                   COVSRT, saturation verdicts, the call's 8 shifted lattices -> one record
 //   qmc_main_kernel<T> wave per (candidate, r)      the lattice sum of the prior call (the FP64-VALU bound part), MI term of r
+//                      (T = 4: wave per four r)     (ITAL_QMC_SHARE_LAST: the chains the full rounds leave over, once for the four)
 //   qmc_combine_kernel thread per candidate         terms of the 2^T patterns in itertools.product order -> mi
 // The records travel through a workspace in HBM (208 B per call at T = 4); the candidates are processed in slabs that fit it.
 template <int T>
@@ -244,7 +269,12 @@ struct Qmc {
     static constexpr int NH = ITAL_QMC_MAIN_NH(T);
     static constexpr int TAILQ = 128 * NH;                    // compaction queue of the Phi^-1 tail branch (in place)
     static constexpr bool PS = ITAL_QMC_MAIN_PS(T), CFL = PS && ITAL_QMC_MAIN_CFL(T);
-    static constexpr int WAVE_DOUBLES = LAT + TAILQ + (CFL ? NCOR + T : 0);
+    // a wave takes RPW consecutive records (sign patterns of one candidate) and evaluates their left-over chains in one round
+    static constexpr bool SHARE = ITAL_QMC_SHARE_LAST && ITAL_QMC_HOTK && ITAL_QMC_FLIP && !PS &&
+                                  QmcRounds<T, NH>::NCL == 1 && ITAL_QMC_SHARE_RECS * QmcRounds<T, NH>::REST <= 64 &&
+                                  NPAT % ITAL_QMC_SHARE_RECS == 0;
+    static constexpr int RPW = SHARE ? ITAL_QMC_SHARE_RECS : 1;
+    static constexpr int WAVE_DOUBLES = LAT + TAILQ + (CFL ? NCOR + T : 0) + (SHARE ? 64 + 2 * RPW + 6 : 0);
     // exp / log coefficients: vector-register operands, or scalar ones where the factor does not occupy the scalar file
     typedef typename std::conditional<(CFL && ITAL_QMC_MAIN_KS(T)), HotKS,
                 typename std::conditional<(ITAL_QMC_MAIN_KEN(T) >= 0), HotKEn<(ITAL_QMC_MAIN_KEN(T) >= 0 ? ITAL_QMC_MAIN_KEN(T) : 0)>,
@@ -505,11 +535,155 @@ __global__ __launch_bounds__(Qmc<T>::PREP_THREADS) void qmc_prep_kernel(ScoreArg
     rec[Q::R_META] = __longlong_as_double(meta);
 }
 
+// The lattice-sum kernel where a wave takes RPW consecutive records (ITAL_QMC_SHARE_LAST): first the left-over chains of all
+// of them in one round -- lane l: record l >> 4, left-over chain l & 15, its call read straight from the record -- then per
+// record the full rounds and the additions qmc_lane_sum makes, in its order: lanes 0 .. 15 add their left-over chain to their
+// partial, the others 0; the same wave_sum, division and flag.  The sums come out bit for bit as with one record per wave.
+template <int T>
+__device__ __forceinline__ void qmc_main_shared(const uint8_t* __restrict__ alive, int64_t slab_lo, int64_t slab_n,
+                                                const double* __restrict__ recs, const double* __restrict__ vk, double eps,
+                                                int label_mode, double* __restrict__ terms) {
+    using Q = Qmc<T>;
+    using R = QmcRounds<T, Q::NH>;
+    extern __shared__ double lds_all[];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t item0 = ((int64_t)blockIdx.x * 4 + wid) * Q::RPW;   // first of the wave's (candidate of the slab, sign pattern)
+    const int64_t i = item0 >> T;                                     // (RPW divides 2^T: one candidate)
+    if (i >= slab_n) return;
+    if (!alive[slab_lo + i]) return;
+    double* lat = lds_all + (size_t)wid * Q::WAVE_DOUBLES;
+    double* tailq = lat + Q::LAT;
+    int first = -1;                                                   // first record that is integrated
+    for (int j = Q::RPW - 1; j >= 0; j--)
+        if (__double_as_longlong(uniform_f64(recs[(item0 + j) * Q::REC + Q::R_META])) & META_EVAL) first = j;
+    double* lastv = tailq + Q::TAILQ;      // [64] values of the left-over chains, [RPW] prior probabilities, [RPW] first widths, [6] `keep`
+    typename Q::Coef kk;
+    kk.load();
+    if (first >= 0) {
+        // ---------------- the left-over chains: item FULL * 64 * NH + ((l & 15) >> 1), the antithetic partner on odd lanes (as
+        // qmc_lane_sum lays them out on lanes 0 .. 15).  Lanes without an integrated record run a dead copy of the first one.
+        const int j_own = lane >> 4;
+        bool dead = j_own >= Q::RPW;
+        if (!dead) dead = !(__double_as_longlong(recs[(item0 + j_own) * Q::REC + Q::R_META]) & META_EVAL);
+        const double* rec = recs + (item0 + (dead ? first : j_own)) * Q::REC;
+        const unsigned flips = (unsigned)(__double_as_longlong(rec[Q::R_META]) >> 8) & ((1u << T) - 1u);
+        double cf[Q::NCOR > 0 ? Q::NCOR : 1], lm[T], xx[Q::NDIM > 0 ? Q::NDIM : 1];
+#pragma unroll
+        for (int q = 0; q < Q::NCOR; q++) cf[q] = rec[q];
+#pragma unroll
+        for (int q = 0; q < T; q++) lm[q] = rec[Q::R_LIM + q];
+        const unsigned int* shifts = reinterpret_cast<const unsigned int*>(rec + Q::R_LAT);
+        const unsigned char* perm = reinterpret_cast<const unsigned char*>(rec + Q::R_LAT + 4 * Q::NDIM);
+        const int it = R::FULL * 64 * Q::NH + ((lane & 15) >> 1);
+        const int sft = it / Q::PRIME;
+        const int k = it - sft * Q::PRIME + 1;
+#pragma unroll
+        for (int j = 0; j < Q::NDIM; j++) {
+            const int q = sft * Q::NDIM + j;      // generator and shift as the unpacking below forms them
+            const double gen = vk[perm[q]];
+            const double shf = (double)shifts[q] * MRG_INVMP1 + (((flips >> (q % Q::NDIM)) & 1u) ? 0.5 : 0.0);
+            const double v = k * gen + shf;
+            const double fr = v - floor(v);
+            const double x = fabs(2 * fr - 1);
+            xx[j] = (lane & 1) ? 1 - x : x;
+        }
+        double w0;
+        lastv[lane] = eval_chain_lanes<T, typename Q::Coef>(xx, dead, cf, lm, flips, tailq, lane, kk, w0);
+        if ((lane & 15) == 0 && j_own < Q::RPW) lastv[64 + Q::RPW + j_own] = w0;
+    }
+    // ---------------- per record: the full rounds.  The scalar file is full inside the lattice sum (factor, limits, the
+    // literals of Phi and Phi^-1): what the loop over the records would carry through it in scalar registers -- the kernel's
+    // arguments, the record's number -- pushed the factor out into lane spills, 78 lane reads per round.  So the arguments wait
+    // in wave-private LDS and the counter in a vector register, and each use forms its scalars again.
+    double* keep = lastv + 64 + 2 * Q::RPW;      // [KEEP] recs, vk, terms, eps, label_mode, item0
+    if (lane == 0) {
+        keep[0] = __longlong_as_double((long long)recs);
+        keep[1] = __longlong_as_double((long long)vk);
+        keep[2] = __longlong_as_double((long long)terms);
+        keep[3] = eps;
+        keep[4] = __longlong_as_double((long long)label_mode);
+        keep[5] = __longlong_as_double(item0);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int jv = 0;
+    for (;;) {
+        // (opaque lane too: what a record's work derives from it -- addresses, masks -- is formed per record, not hoisted out
+        // of this loop and carried through the lattice sum)
+        int ln = lane;
+        __asm__ volatile("" : "+v"(ln), "+v"(jv));
+        const int j = __builtin_amdgcn_readfirstlane(jv);
+        if (j >= Q::RPW) break;
+        const double* rec = reinterpret_cast<const double*>(__double_as_longlong(uniform_f64(keep[0]))) +
+                            (__double_as_longlong(uniform_f64(keep[5])) + j) * Q::REC;
+        const long long meta = __double_as_longlong(uniform_f64(rec[Q::R_META]));
+        double pr = (meta & META_PRIOR_ONE) ? 1.0 : 0.0;
+        if (meta & META_EVAL) {
+            const unsigned flips = (unsigned)(meta >> 8) & ((1u << T) - 1u);   // variables bounded below
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");            // (the lattice of the record before is read)
+            __builtin_amdgcn_wave_barrier();
+            {   // unpack the lattices: generator = vk[index], shift = integer * 1/(m1 + 1) exactly as MVNUNI forms it
+                const double* vk_j = reinterpret_cast<const double*>(__double_as_longlong(uniform_f64(keep[1])));
+                const unsigned int* shifts = reinterpret_cast<const unsigned int*>(rec + Q::R_LAT);
+                const unsigned char* perm = reinterpret_cast<const unsigned char*>(rec + Q::R_LAT + 4 * Q::NDIM);
+                for (int q = ln; q < 8 * Q::NDIM; q += 64) {
+                    lat[q] = vk_j[perm[q]];
+                    lat[8 * Q::NDIM + q] = (double)shifts[q] * MRG_INVMP1 + (((flips >> (q % Q::NDIM)) & 1u) ? 0.5 : 0.0);
+                }
+            }
+            double cf[Q::NCOR > 0 ? Q::NCOR : 1], lm[T];
+#pragma unroll
+            for (int q = 0; q < Q::NCOR; q++) cf[q] = q >= Q::NCOR - ITAL_QMC_SHARE_VCF ? rec[q] : uniform_f64(rec[q]);
+#pragma unroll
+            for (int q = 0; q < T; q++) lm[q] = uniform_f64(rec[Q::R_LIM + q]);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const double w0 = lastv[64 + Q::RPW + j];      // (a vector value, for the same reason)
+            const double part = qmc_lane_sum_full<T, typename Q::Coef, Q::NH>(lat, w0, cf, lm, flips, tailq, ln, kk);
+            __asm__ volatile("" : "+v"(jv));
+            const int j2 = __builtin_amdgcn_readfirstlane(jv);
+            const double acc = part + (ln < 16 ? lastv[16 * j2 + ln] : 0.0);
+            pr = wave_sum(acc) / (16.0 * Q::PRIME);
+            // (the flag for qmc_exact_kernel: see qmc_main_kernel)
+#ifndef ITAL_NO_EXACT_FLAG
+            if ((pr > 1.0 - EXACT_BAND || pr < EXACT_BAND) && ln == 0 && __double_as_longlong(keep[4]) != 0) {
+                double* rm = reinterpret_cast<double*>(__double_as_longlong(keep[0])) + (__double_as_longlong(keep[5]) + j2) * Q::REC + Q::R_META;
+                *rm = __longlong_as_double(__double_as_longlong(*rm) | META_EXACT);
+            }
+#endif
+        }
+        __asm__ volatile("" : "+v"(jv));
+        if (ln == 0) lastv[64 + __builtin_amdgcn_readfirstlane(jv)] = pr;
+        jv = jv + 1;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < Q::RPW) {      // the terms of the wave's records in one pass
+        const double* recs_k = reinterpret_cast<const double*>(__double_as_longlong(keep[0]));
+        double* terms_k = reinterpret_cast<double*>(__double_as_longlong(keep[2]));
+        const long long item_l = __double_as_longlong(keep[5]) + lane;
+        const double eps_k = keep[3];
+        const double pr_l = lastv[64 + lane];
+        const long long meta_l = __double_as_longlong(recs_k[item_l * Q::REC + Q::R_META]);
+        const double pu = (meta_l & META_POST_ONE) ? 1.0 : 0.0;
+        const double cur = log_eps(pu, eps_k) - log_eps(pr_l, eps_k);   // perfect user: likelihood weight 1 (ital.py:208)
+        terms_k[item_l] = __double_as_longlong(keep[4]) == 0 ? cur * pr_l : cur;
+    }
+}
+
 template <int T>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ITAL_QMC_WAVES(T), ITAL_QMC_WAVES(T)))) void qmc_main_kernel(
     const uint8_t* __restrict__ alive, int64_t slab_lo, int64_t slab_n, const double* __restrict__ recs,
     const double* __restrict__ vk, double eps, int label_mode, double* __restrict__ terms) {
     using Q = Qmc<T>;
+    if constexpr (Q::SHARE) {
+        qmc_main_shared<T>(alive, slab_lo, slab_n, recs, vk, eps, label_mode, terms);
+        return;
+    }
     extern __shared__ double lds_all[];
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -688,7 +862,7 @@ static int launch_qmc(const ScoreArgs& a, double* work, int64_t work_doubles, in
         ITAL_LAUNCH(qmc_prep_kernel<T>, dim3((unsigned)((n + Q::PREP_THREADS - 1) / Q::PREP_THREADS), Q::NPAT),
                            dim3(Q::PREP_THREADS), lds_prep, stream, a, lo, n, seeds, recs);
         if (ev0 && lo == 0) (void)hipEventRecord(ev0, stream);
-        ITAL_LAUNCH(qmc_main_kernel<T>, dim3((unsigned)((n * Q::NPAT + 3) / 4)), dim3(256), lds_main, stream, a.alive, lo,
+        ITAL_LAUNCH(qmc_main_kernel<T>, dim3((unsigned)((n * Q::NPAT + 4 * Q::RPW - 1) / (4 * Q::RPW))), dim3(256), lds_main, stream, a.alive, lo,
                            n, recs, a.vk, a.eps, a.label_mode, terms);
         if (ev1 && lo + n >= a.n_cand) (void)hipEventRecord(ev1, stream);
         if (a.label_mode != 0) {
