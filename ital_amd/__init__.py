@@ -8,7 +8,7 @@ The arithmetic lives in hand-written HIP kernels (ital_amd/csrc, C ABI in includ
 from . import mvn_stream
 from .mvn_stream import GLOBAL as mvn_global_stream
 
-__all__ = ["ITAL", "MCMI_min", "GaussianProcess", "ActiveRetrievalBase", "mvn_stream", "mvn_global_stream", "serving_mode"]
+__all__ = ["ITAL", "MCMI_min", "AdaptAL", "GaussianProcess", "ActiveRetrievalBase", "mvn_stream", "mvn_global_stream", "serving_mode"]
 
 
 def serving_mode():
@@ -35,4 +35,7 @@ def __getattr__(name):
     if name == "MCMI_min":
         from .mcmi import MCMI_min
         return MCMI_min
+    if name == "AdaptAL":
+        from .adapt_al import AdaptAL
+        return AdaptAL
     raise AttributeError(name)

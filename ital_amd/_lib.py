@@ -1,4 +1,5 @@
-"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h and include/ital_dense.h).
+"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h and
+include/ital_adapt.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -189,6 +190,16 @@ DENSE_SIGNATURES = {
 }
 
 
+#: the kernels of the AdaptAL learner, declared in include/ital_adapt.h
+ADAPT_SIGNATURES = {
+    "ital_chol_inv_diag": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ital_chol_inv_diag_workspace": (c_int64, [c_int]),
+    "ital_adapt_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p]),
+    "ital_adapt_error": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_double, c_void_p,
+                                 c_void_p, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -207,7 +218,8 @@ def load(path=LIB_PATH):
     except ImportError:
         pass
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
+            list(ADAPT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -4,7 +4,7 @@ TopscoringSampling, BorderlineSampling, BorderlineDiversitySampling, VarianceSam
 `use_correlations`), UncertaintySampling, EntropySampling (the orthant kernel of the ITAL scorer) and EMOC (the FP64
 MFMA covariance tiles of MCMI) -- reference ital/baseline_methods.py:12-155, :203-287, :338-381.  They exist so that the
 reference's comparison tables run through `ital_amd.harness` against the same GP; the remaining baselines (SUD, RBMAL,
-TCAL, USDM, AdaptAL) use models of their own and are out of scope.
+TCAL, USDM) use models of their own and are out of scope; AdaptAL is a learner of its own (ital_amd/adapt_al.py).
 """
 import numpy as np
 import torch

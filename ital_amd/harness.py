@@ -1,7 +1,7 @@
 """Experiment harness for the device learners: counterpart of the reference's `utils.py` (config reader, learner
 registry, NDCG / AUC), `datasets.py` (the loaders whose data ship with the reference or with scikit-learn) and
 `run_experiment.py` (simulated relevance-feedback loop, AP / NDCG table), so that the reference's `configs/*.conf`
-run unchanged against `ital_amd.ITAL` / `ital_amd.MCMI_min`:
+run unchanged against `ital_amd.ITAL` / `ital_amd.MCMI_min` / `ital_amd.AdaptAL`:
 
     python -m ital_amd.harness configs/iris.conf [--rounds=3 --repetitions=2 ...]
 
@@ -56,14 +56,14 @@ def read_config_file(config_file, section, overrides):
 
 
 def _learners():
-    from . import ITAL, MCMI_min
+    from . import ITAL, AdaptAL, MCMI_min
     from .baselines import LEARNERS as ranking
-    table = {"ITAL": ITAL, "MCMI": MCMI_min}
+    table = {"ITAL": ITAL, "MCMI": MCMI_min, "AdaptAL": AdaptAL}
     table.update(ranking)
     return table
 
 
-BASELINES = ("SUD", "RBMAL", "TCAL", "USDM", "AdaptAL")
+BASELINES = ("SUD", "RBMAL", "TCAL", "USDM")
 
 
 def make_learner(method, data, learner_config, **placement):
@@ -71,7 +71,7 @@ def make_learner(method, data, learner_config, **placement):
     if method not in table:
         if method in BASELINES:
             raise NotImplementedError("learner %r is one of the reference's comparison baselines that are not part of the "
-                                      "MI355X path (ITAL, MCMI and the GP-sharing baselines random / topscoring / border / "
+                                      "MI355X path (ITAL, MCMI, AdaptAL and the GP-sharing baselines random / topscoring / border / "
                                       "border_div / var / unc / entropy / EMOC are)" % method)
         raise KeyError("unknown learner %r" % method)
     return table[method](data, **learner_config, **placement)
