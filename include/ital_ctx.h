@@ -63,6 +63,16 @@ int ital_ctx_top_results(ital_ctx* ctx, int k, int64_t* idx, hipStream_t stream)
  * before the first label. */
 int ital_ctx_predict(ital_ctx* ctx, const double* Xt, int64_t nt, double* mean, double* variance, hipStream_t stream);
 
+/* Takes the labels of idx[0 .. c) back (global sample indices, host memory): each leaves the labelled set by a Cholesky row
+ * deletion and one sweep over the whitened block (ital_gp_remove, ital_revoke.h), highest labelled position first, and is a
+ * candidate again afterwards; ital_ctx_update may then label it anew.  What the reference refuses (RuntimeError 'Cannot
+ * change feedback once given.', reference ital/retrieval_base.py:183-189) and could only undo by a fit from scratch on the
+ * surviving labels (reference ital/gp.py:141-161).  The context remembers the insertion order of its labelled samples for
+ * this.  Several ranks make the same call (no exchange: factor and labels are replicated, every rank sweeps its own
+ * columns).  -22 for a NULL context or list, c < 1, a sample that has no label, a sample named twice; nothing is changed
+ * then. */
+int ital_ctx_revoke(ital_ctx* ctx, const int64_t* idx, int c, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

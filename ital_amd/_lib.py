@@ -1,5 +1,5 @@
-"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h and
-include/ital_adapt.h).
+"""ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
+include/ital_adapt.h and include/ital_revoke.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -175,6 +175,7 @@ CTX_SIGNATURES = {
     "ital_ctx_mcmi_fetch": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "ital_ctx_top_results": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "ital_ctx_predict": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ital_ctx_revoke": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 
@@ -200,6 +201,20 @@ ADAPT_SIGNATURES = {
 }
 
 
+class ItalRemoveDesc(ctypes.Structure):
+    """ital_remove_desc (include/ital_revoke.h): the GP state and the labelled position that leaves it."""
+    _fields_ = [("XT", c_void_p), ("XTn", c_void_p), ("ldx", c_int), ("L", c_void_p), ("ldl", c_int), ("alpha", c_void_p),
+                ("V", c_void_p), ("ldv", c_int64), ("n", c_int64), ("mu", c_void_p), ("s2", c_void_p), ("m", c_int), ("p", c_int),
+                ("work", c_void_p), ("work_doubles", c_int64), ("status", c_void_p)]
+
+
+#: taking a label back, declared in include/ital_revoke.h
+REVOKE_SIGNATURES = {
+    "ital_gp_remove": (c_int, [ctypes.POINTER(ItalRemoveDesc), c_void_p]),
+    "ital_gp_remove_workspace": (c_int64, [c_int]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -219,7 +234,7 @@ def load(path=LIB_PATH):
         pass
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
-            list(ADAPT_SIGNATURES.items()):
+            list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

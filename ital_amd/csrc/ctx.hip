@@ -27,6 +27,7 @@
 #include "ital_ctx.h"
 #include "ital_hip.h"
 #include "ital_internal.h"
+#include "ital_revoke.h"
 
 struct ital_ctx {
     int64_t n_total = 0, row0 = 0, row1 = 0, n = 0, ldv = 0;
@@ -51,6 +52,8 @@ struct ital_ctx {
     int mvn_state[6] = {};
     std::vector<uint8_t> seen;          // [n_total] labelled (the reference's relevant / irrelevant ids)
     int64_t n_seen = 0;
+    std::vector<int64_t> order;         // the labelled samples in insertion order: order[p] sits at position p of L / V / XT
+    double* rwork = nullptr;            // ital_gp_remove_workspace(cap) doubles, allocated by the first ital_ctx_revoke
     std::vector<int64_t> last_picks;    // the batch of the last fetch (its feature rows sit in batch.XB on every rank)
     std::vector<void*> owned;
     // user model (ital_ctx_set_model); without one ital_ctx_fetch is the perfect-user layer above (-71 and all)
@@ -213,6 +216,7 @@ extern "C" int ital_ctx_fit(ital_ctx* c, const double* rows, int on_device, hipS
     c->m = 0;
     std::fill(c->seen.begin(), c->seen.end(), 0);
     c->n_seen = 0;
+    c->order.clear();
     c->last_picks.clear();
     c->fitted = true;
     return 0;
@@ -285,8 +289,44 @@ extern "C" int ital_ctx_update(ital_ctx* c, const int64_t* idx, const double* y,
         c->m += cc;
     }
     for (int j = 0; j < c_new; j++) c->seen[(size_t)idx[j]] = 1;
+    c->order.insert(c->order.end(), idx, idx + c_new);
     c->n_seen += c_new;
     c->last_picks.clear();
+    return 0;
+}
+
+// Takes labels back (include/ital_ctx.h): stands in for the RuntimeError of reference retrieval_base.py:183-189 and the fit
+// from scratch on the survivors, reference gp.py:141-161.  One ital_gp_remove per sample, highest position first: those
+// sweeps are the shortest and shift nothing below them.
+extern "C" int ital_ctx_revoke(ital_ctx* c, const int64_t* idx, int c_rev, hipStream_t stream) {
+    if (!c || !c->fitted || !idx || c_rev < 1) return ital_fail(-22, "ital_ctx_revoke: bad arguments");
+    std::vector<int> pos(c_rev);
+    for (int j = 0; j < c_rev; j++) {
+        if (idx[j] < 0 || idx[j] >= c->n_total || !c->seen[(size_t)idx[j]])
+            return ital_fail(-22, "ital_ctx_revoke: a sample that has no label");
+        const auto it = std::find(c->order.begin(), c->order.end(), idx[j]);
+        if (it == c->order.end()) return ital_fail(-22, "ital_ctx_revoke: a sample that has no label");
+        pos[j] = (int)(it - c->order.begin());
+    }
+    std::sort(pos.begin(), pos.end(), [](int a, int b) { return a > b; });
+    if (std::adjacent_find(pos.begin(), pos.end()) != pos.end()) return ital_fail(-22, "ital_ctx_revoke: a sample named twice");
+    if (!c->rwork) {
+        c->rwork = dalloc<double>(c, (size_t)ital_gp_remove_workspace(c->cap));
+        if (!c->rwork) return ital_fail(-12, "ital_ctx_revoke: out of device memory");
+    }
+    for (int p : pos) {
+        ital_remove_desc r = {};
+        r.XT = c->XT; r.XTn = c->XTn; r.ldx = c->ldx; r.L = c->L; r.ldl = c->cap; r.alpha = c->alpha;
+        r.V = c->V; r.ldv = c->ldv; r.n = c->n; r.mu = c->mu; r.s2 = c->s2; r.m = c->m; r.p = p;
+        r.work = c->rwork; r.work_doubles = ital_gp_remove_workspace(c->cap); r.status = c->status;
+        const int rc = ital_gp_remove(&r, stream);
+        if (rc) return rc;
+        c->seen[(size_t)c->order[(size_t)p]] = 0;
+        c->order.erase(c->order.begin() + p);
+        c->n_seen--;
+        c->m--;
+    }
+    if (hipStreamSynchronize(stream) != hipSuccess) return ital_fail(-5, "ital_ctx_revoke: stream error");
     return 0;
 }
 

@@ -34,6 +34,23 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def appends_after_remove(appends, p):
+    """`appends` (sizes of the calls that built the labelled set, in order; negative: a group of queries) once the sample at
+    labelled position `p` has left: the group that held it shrinks by one -- possibly to 0, which load_state_dict skips --
+    so that a replay of the list appends exactly the surviving sequence.  Query groups are never touched: a position
+    inside one is a ValueError, like a position outside the labelled set."""
+    out = list(appends)
+    at = 0
+    for g, c in enumerate(out):
+        if at <= p < at + abs(c):
+            if c < 0:
+                raise ValueError("labelled position %d is a query" % p)
+            out[g] = c - 1
+            return out
+        at += abs(c)
+    raise ValueError("labelled position %d outside the %d labelled samples" % (p, at))
+
+
 class GaussianProcess(object):
     """GP on a row shard of `data` (rows [row0, row1) on this rank).
 
@@ -317,6 +334,48 @@ class GaussianProcess(object):
                                          L21.data_ptr() + 8 * m, _ptr(self.alpha[m:m + c]), _ptr(self.V), self.ldv, m,
                                          float(self.var), float(self.length_scale), _ptr(self.mu), _ptr(self.s2), st))
             self.m += c
+
+    def remove(self, ind):
+        """Takes labelled samples (data indices) out of the model again: afterwards the state is what fitting the surviving
+        samples in their order gives (up to rounding).  The reference has no such call -- a label, once given, stays
+        (retrieval_base.py:183-189), its way back is fit() on the survivors, gp.py:141-161; here each sample leaves by a row
+        deletion of the Cholesky factor and one orthogonal sweep over the whitened block (ital_gp_remove), highest
+        labelled position first: those sweeps are the shortest and shift nothing below them.  Every rank makes the same
+        call (L, alpha, XT are replicated, V is column-sharded: no exchange beyond the replicated means).
+
+        ValueError for an index that has no label, one named twice and for a query row (>= number of samples: queries are
+        part of the learner's construction); nothing is changed then.  An empty list is a no-op."""
+        ind = [int(i) for i in ind]
+        if not ind:
+            return self
+        if len(set(ind)) != len(ind):
+            raise ValueError("a sample is named twice")
+        pos_of = {i: p for p, i in enumerate(self.ind)}
+        for i in ind:
+            if i >= self.n_total:
+                raise ValueError("%d is a query row: queries cannot be removed" % i)
+            if i not in pos_of:
+                raise ValueError("sample %d has no label" % i)
+        lib, st = self._lib, _stream()
+        need = int(lib.ital_gp_remove_workspace(self.cap))
+        work = getattr(self, "_remove_work", None)
+        if work is None or work.numel() < need:
+            self._remove_work = work = torch.empty(need, dtype=torch.float64, device=self.device)
+        r = _lib.ItalRemoveDesc()
+        r.XT, r.XTn, r.ldx, r.L, r.ldl, r.alpha = _ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(self.L), self.cap, _ptr(self.alpha)
+        r.V, r.ldv, r.n, r.mu, r.s2 = _ptr(self.V), self.ldv, self.n, _ptr(self.mu), _ptr(self.s2)
+        r.work, r.work_doubles, r.status = _ptr(work), work.numel(), _ptr(self.status)
+        for p in sorted((pos_of[i] for i in ind), reverse=True):
+            r.m, r.p = self.m, p
+            check(lib.ital_gp_remove(ctypes.byref(r), st))
+            self.appends = appends_after_remove(self.appends, p)
+            del self.ind[p]
+            self.y = np.delete(self.y, p)
+            self.m -= 1
+        if self.m == 0:
+            self.reset()              # nothing is left: the prior, exactly (the kernels left rows >= m of V, L, XT zero)
+        self._replicate_mean()
+        return self
 
     def check_status(self, status=None):
         """Raises if a kernel flagged a numerical failure.  `status`: the word as already downloaded (e.g. the OR over all

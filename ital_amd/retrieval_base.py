@@ -306,6 +306,42 @@ class ActiveRetrievalBase(object):
         self.unnameable_ids.update(unnameable)
         self._unseen_after(rel + irr + new_unnameable, sizes_before)
 
+    def revoke(self, ids):
+        """Takes the feedback for `ids` back: they leave the relevant / irrelevant / unnameable ids and -- the labelled ones
+        -- the GP (GaussianProcess.remove: a Cholesky row deletion and one sweep on the device), and are candidates again.
+        The reference has no way back from a label (RuntimeError 'Cannot change feedback once given.',
+        retrieval_base.py:183-189) short of reset() and a replay of the surviving feedback, gp.py:141-161.  `rounds` stays
+        as it is.  ValueError for an id that never got feedback (nothing is changed then).  Several ranks: every rank makes
+        the same call, like update()."""
+        ids = list(dict.fromkeys(int(i) for i in ids))
+        for i in ids:
+            if not (i in self.relevant_ids or i in self.irrelevant_ids or i in self.unnameable_ids):
+                raise ValueError("sample %d never got feedback" % i)
+        labelled = [i for i in ids if i in self.relevant_ids or i in self.irrelevant_ids]
+        if labelled:
+            self.gp.remove(labelled)
+        for i in ids:
+            # in-place changes of the three IdSets: the unseen list and a device candidate list rebuild on their next use
+            self.relevant_ids.discard(i)
+            self.irrelevant_ids.discard(i)
+            self.unnameable_ids.discard(i)
+        self.__dict__["_unseen"] = None
+        self._fitted = self.gp.m > 0
+
+    def relabel(self, feedback):
+        """update(feedback) for a user who corrects themselves: the ids of `feedback` whose stored feedback differs from the
+        new one are revoked first, then `feedback` is applied as update() applies it.  update() itself keeps refusing a
+        changed label, as the reference does (retrieval_base.py:183-189)."""
+        changed = []
+        for i, fb in feedback.items():
+            old = 1 if i in self.relevant_ids else -1 if i in self.irrelevant_ids else 0 if i in self.unnameable_ids else None
+            new = 1 if fb > 0 else -1 if fb < 0 else 0
+            if old is not None and old != new:
+                changed.append(i)
+        if changed:
+            self.revoke(changed)
+        self.update(feedback)
+
     def _batch_rows(self):
         """Feature rows of the last fetched batch as kept (replicated) in the device batch state, or None."""
         last = getattr(self, "_last_batch", None)
