@@ -10,49 +10,29 @@ kernel enqueued on one stream, with no host round trip inside a round:
                          next cross-covariance col.  ital_cross_cov_cols  (predict_cov_batch, ital.py:586)
 
 Candidates are sharded by rows across ranks; the per-step exchange is ONE fixed-size record per rank.
+
+This module holds the learner, its fast paths (`_select_round`: a whole round as one call below the C ABI; `_select_steps`:
+step by step) and their dispatch.  The round of every other option (`_fetch_generic`) is `_generic_round.GenericRound`, the
+host sampling of the Monte-Carlo switches `_mc_sampler`, the launches all greedy loops share (selection of a step, the new
+member's covariance column, lattice tables, workspace) `_batch`.
 """
 import ctypes
 import os
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _lib, mvn_stream, sharding
-from ._lib import (ITAL_GENERIC_MAX_CALLS, ITAL_GENERIC_MAX_DIM, ITAL_GENERIC_MAX_REL, ITAL_JUMP_BITS, ITAL_MAX_T, ITAL_REC_HEADER, ItalBatch,
-                   ItalGscoreDesc, ItalScoreDesc, check)
-from ._batch import make_batch_buffers
-from .gp import _pad16, _ptr, _stream
+from . import _lib, _mc_sampler, mvn_stream, sharding
+from ._lib import ITAL_GENERIC_MAX_CALLS, ITAL_GENERIC_MAX_DIM, ITAL_GENERIC_MAX_REL, ITAL_MAX_T, ItalScoreDesc, check
+from ._batch import (FUSED_LAUNCH_MAX as _FUSED_LAUNCH_MAX, LABEL_MODES as _LABEL_MODES, Scored, fill_score_desc,
+                     fill_score_select, gp_model, lattice_tables, make_batch_buffers, member_column, qmc_work, select_step)
+from ._generic_round import GenericRound
+from ._mc_sampler import range_cuts as _range_cuts   # noqa: F401 -- tests/test_host_logic.py imports it from here
+from .gp import _ptr, _stream
 from .retrieval_base import ActiveRetrievalBase, UnseenList
 
-_LABEL_MODES = {"mean": 0, "optimistic": 1, "pessimistic": 2}
-_HOST_THREADS = max(1, min(int(os.environ.get("ITAL_HOST_THREADS", 16)), os.cpu_count() or 1))   # host share of one GPU (Monte-Carlo pattern sampling)
-# pattern sampling: ranges of candidates per greedy step (host / GPU overlap), their minimum size, and the number of
-# variables from which a step is split at all (below, the step's lattice sums are shorter than the host's decompositions:
-# measured at 125 000 x 512, nothing to hide behind; on shards of 262 144 candidates and more from 7 variables on)
-_MC_CHUNKS, _MC_CHUNK_MIN, _MC_CHUNK_FROM = (int(os.environ.get("ITAL_MC_CHUNKS", 4)), int(os.environ.get("ITAL_MC_CHUNK_MIN", 8192)),
-                                             int(os.environ.get("ITAL_MC_CHUNK_FROM", 10)))      # (environment: experiments only)
-_POOL = None
-
-
-def _range_cuts(lo, hi, chunks, smallest=None):
-    """Boundaries of the ranges a step of sampled patterns is scored in: sizes 1 : 2 : 4 : ... over [lo, hi) (the first range is
-    decomposed while the GPU idles, every later one under the lattice sums of the range before), none shorter than `smallest`
-    (default _MC_CHUNK_MIN) unless the whole span is.  Ascending int64 array, first entry lo, last entry hi."""
-    smallest = _MC_CHUNK_MIN if smallest is None else smallest
-    span = hi - lo
-    cuts = lo + (span * ((1 << np.arange(chunks + 1)) - 1)) // ((1 << chunks) - 1)
-    return np.unique(np.concatenate(([lo], cuts[cuts - lo >= min(smallest, span)], [hi])).astype(np.int64))
-
-
-def _host_pool():
-    global _POOL
-    if _POOL is None:
-        _POOL = ThreadPoolExecutor(_HOST_THREADS)
-    return _POOL
 _FUSED_SELECT_MAX = _lib.ITAL_ROUND_MAX_CAND   # per rank, up to this many candidates: arg-max + record (+ resolve) inside the scoring launch
-_FUSED_LAUNCH_MAX = 1 << 18   # one rank, up to this many candidates: ital_select_fused (one workgroup) as the separate selection launch
 
 
 class ITAL(ActiveRetrievalBase):
@@ -113,21 +93,7 @@ class ITAL(ActiveRetrievalBase):
     def _mc_plan(self, nr, fb_mode):
         """Which enumerations the reference replaces by sampling at a step with nr enumerated variables
         (ital.py:293-297, :318-337): (rel sampled?, patterns, feedback sampled?, feedback configurations)."""
-        num_rel = nr * self.monte_carlo_num_rel if self.monte_carlo_num_rel is not None else None
-        rel_mc = num_rel is not None and not (2 ** (nr - 1) < num_rel)
-        npat = num_rel if rel_mc else 2 ** nr
-        num_fb = nr * self.monte_carlo_num_fb if self.monte_carlo_num_fb is not None else None
-        if fb_mode == 3:                 # entropy objective: no simulated feedback at all
-            fb_mc, nfb = False, 0
-        elif fb_mode == 0:
-            fb_mc, nfb = False, 1
-        elif fb_mode == 1:
-            fb_mc = num_fb is not None and not (2 ** (nr - 1) < num_fb)
-            nfb = num_fb if fb_mc else 2 ** nr
-        else:
-            fb_mc = num_fb is not None and not (3 ** nr < 2 * num_fb)
-            nfb = num_fb if fb_mc else 3 ** nr - 1
-        return rel_mc, npat, fb_mc, nfb
+        return _mc_sampler.mc_plan(nr, fb_mode, self.monte_carlo_num_rel, self.monte_carlo_num_fb)
 
     def _unsupported(self, k, n_unseen=0):
         """Reason why the device scorers cannot run this configuration (None if they can)."""
@@ -286,10 +252,7 @@ class ITAL(ActiveRetrievalBase):
     def _qmc_workspace(self, b, t, n_loc):
         """Workspace of the lattice scorer (prepared calls of a slab of candidates), grown on demand up to `qmc_work_bytes`."""
         want = int(_lib.lib().ital_round_workspace(t, max(n_loc, 1), max(self.qmc_work_bytes // 8, 1 << 16)))
-        w = b.get("qmc_work")
-        if w is None or w.numel() < want:
-            b["qmc_work"] = w = torch.empty(want, dtype=torch.float64, device=self.gp.device)
-        return w
+        return qmc_work(b, want, self.gp.device)
 
     def _sel_parts_doubles(self, k, n_loc):
         """Doubles of the block partials of the selection inside the scoring launches of a round of k steps: three per
@@ -307,100 +270,80 @@ class ITAL(ActiveRetrievalBase):
         if self.round_call and self.select_in_scorer and self._round_possible(k, candidates):
             return self._select_round(k, candidates)
         self._dev_list = None
+        return self._select_steps(k, candidates)
+
+    def _user(self):
+        """(noise, eps, label mode) of ital_score_desc."""
+        return float(self.noise), float(self.eps), _LABEL_MODES[self.label_estimation]
+
+    def _step_desc(self, b, scored, t, k, n_alive, tail, fused):
+        """ital_score_desc of greedy step t of the step-by-step path (tail: the scoring launch ends with the selection)."""
+        lib, gp = _lib.lib(), self.gp
+        n_loc = scored.n
+        desc = ItalScoreDesc()
+        desc.t = t
+        fill_score_desc(desc, gp, b, scored, self._user())
+        if t >= 3:
+            jump, jumppat, vk = lattice_tables(b, t, gp.device)
+            desc.jump, desc.jumppat, desc.vk = _ptr(jump), _ptr(jumppat), _ptr(vk)
+            for j in range(6):
+                desc.seed[j] = mvn_stream.GLOBAL.state[j]
+            work = self._qmc_workspace(b, t, n_loc)
+            desc.work, desc.work_doubles = _ptr(work), work.numel()
+            if self.profile is not None and n_loc > 0:
+                # the lattice-sum kernel alone, bracketed by events the library records on the launch stream (an
+                # event has to be recorded once before its handle exists: the pool's events are, see bench.py).
+                # Every record is a barrier packet in the queue (~4 us of idle GPU in a 3 ms round), so the step
+                # as a whole is only bracketed where no kernel-level pair exists
+                k0, k1 = self._event(), self._event()
+                desc.ev_start, desc.ev_stop = k0.cuda_event, k1.cuda_event
+                # several slabs: the pair spans first .. last lattice sum incl. the launches between them
+                slabs = -(-n_loc // max(work.numel() // int(lib.ital_score_workspace(t, 1)), 1))
+                self.profile.append(("qmc_main" if slabs == 1 else "qmc_slabs%d" % slabs, t,
+                                     n_alive if not gp.collective else n_loc, k0, k1))
+        if tail:
+            # the scoring launch ends with the selection itself (the block that finishes last selects): one rank --
+            # arg-max, record and batch bookkeeping, no selection launch at all; several ranks -- arg-max and record
+            # (what ital_select_local does in a single-workgroup launch of its own), exchange and resolve follow
+            parts = b.get("sel_parts")
+            if parts is None or parts.numel() < self._sel_parts_doubles(k, n_loc):
+                b["sel_parts"] = torch.empty(self._sel_parts_doubles(k, n_loc), dtype=torch.float64, device=gp.device)
+                b["sel_counter"] = torch.zeros(1, dtype=torch.int32, device=gp.device)
+            fill_score_select(desc, gp, b, gp.m, b["ret"] if fused else None)
+        return desc
+
+    def _select_steps(self, k, candidates):
+        """_select step by step from Python: per greedy step the scoring launch, the selection (inside it, or as launches
+        of its own with the ranks' exchange between them) and the new member's covariance column."""
+        gp = self.gp
         lib = _lib.lib()
-        dev = gp.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(gp.device):
             b = self._buffers(k)
             st = _stream()
             # ---- candidate shard of this rank (list positions keep their global numbering)
             cand, n_loc, pos_offset, cand_d, gpos_d, alive = self._shard(candidates, b)
             mi = b["mi"]                                   # every live position is written by the scorer
+            scored = Scored(mi, cand_d, alive, n_loc, pos_offset, gpos_d, gp.row0)
             self.last_scores = []
             stream = mvn_stream.GLOBAL
             saved_stream = (stream.state, stream.draws)
             n_alive = len(candidates)
             b["ret"][b["kmax"]:].zero_()      # the resolve steps OR every rank's status word into this slot
             for t in range(1, k + 1):
-                desc = ItalScoreDesc()
-                desc.t = t
-                desc.n_cand = n_loc
-                desc.cand, desc.alive, desc.mu, desc.s2 = _ptr(cand_d), _ptr(alive), _ptr(gp.mu), _ptr(gp.s2)
-                desc.C, desc.ldc = _ptr(b["C"]), gp.ldv
-                desc.row_offset, desc.pos_offset, desc.gpos = gp.row0, pos_offset, _ptr(gpos_d)
-                desc.batch = b["batch"]
-                desc.noise, desc.eps = float(self.noise), float(self.eps)
-                desc.label_mode = _LABEL_MODES[self.label_estimation]
-                desc.mi = _ptr(mi)
-                desc.status = _ptr(gp.status)
-                if t >= 3:
-                    if t not in b["jump"]:
-                        b["jump"][t] = torch.from_numpy(mvn_stream.jump_table(t, ITAL_JUMP_BITS)).to(dev)
-                        b["jumppat"][t] = torch.from_numpy(mvn_stream.jump_pattern_table(t)).to(dev)
-                        b["vk"][t] = torch.from_numpy(mvn_stream.korobov_vk(t)).to(dev)
-                    desc.jump, desc.jumppat, desc.vk = _ptr(b["jump"][t]), _ptr(b["jumppat"][t]), _ptr(b["vk"][t])
-                    for j in range(6):
-                        desc.seed[j] = stream.state[j]
-                    work = self._qmc_workspace(b, t, n_loc)
-                    desc.work, desc.work_doubles = _ptr(work), work.numel()
-                    if self.profile is not None and n_loc > 0:
-                        # the lattice-sum kernel alone, bracketed by events the library records on the launch stream (an
-                        # event has to be recorded once before its handle exists: the pool's events are, see bench.py).
-                        # Every record is a barrier packet in the queue (~4 us of idle GPU in a 3 ms round), so the step
-                        # as a whole is only bracketed where no kernel-level pair exists
-                        k0, k1 = self._event(), self._event()
-                        desc.ev_start, desc.ev_stop = k0.cuda_event, k1.cuda_event
-                        # several slabs: the pair spans first .. last lattice sum incl. the launches between them
-                        slabs = -(-n_loc // max(work.numel() // int(lib.ital_score_workspace(t, 1)), 1))
-                        self.profile.append(("qmc_main" if slabs == 1 else "qmc_slabs%d" % slabs, t,
-                                             n_alive if not gp.collective else n_loc, k0, k1))
                 tail = self.select_in_scorer and 0 < n_loc <= _FUSED_SELECT_MAX
                 fused = not gp.collective and 0 < n_loc <= (_FUSED_SELECT_MAX if tail else _FUSED_LAUNCH_MAX)
-                if tail:
-                    # the scoring launch ends with the selection itself (the block that finishes last selects): one rank --
-                    # arg-max, record and batch bookkeeping, no selection launch at all; several ranks -- arg-max and record
-                    # (what ital_select_local does in a single-workgroup launch of its own), exchange and resolve follow
-                    parts = b.get("sel_parts")
-                    if parts is None or parts.numel() < self._sel_parts_doubles(k, n_loc):
-                        b["sel_parts"] = parts = torch.empty(self._sel_parts_doubles(k, n_loc), dtype=torch.float64, device=dev)
-                        b["sel_counter"] = torch.zeros(1, dtype=torch.int32, device=dev)
-                    desc.sel_X, desc.sel_xnorm, desc.sel_ldx = _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx
-                    desc.sel_V, desc.sel_ldv, desc.sel_m, desc.sel_ldw, desc.sel_rank = _ptr(gp.V), gp.ldv, gp.m, gp.cap, gp.rank
-                    desc.sel_record, desc.sel_ret = _ptr(b["rec"]), (_ptr(b["ret"]) if fused else None)
-                    desc.sel_parts, desc.sel_parts_len, desc.sel_counter = _ptr(parts), parts.numel(), _ptr(b["sel_counter"])
+                desc = self._step_desc(b, scored, t, k, n_alive, tail, fused)
                 ev0 = self._mark() if t < 3 else None
                 check(lib.ital_score_step(ctypes.byref(desc), st))
                 if t < 3:
                     self._mark("score", t, n_alive, ev0)
                 if self.keep_scores:
                     self.last_scores.append(mi.clone())
-                if tail and fused:
-                    pass
-                elif fused:
-                    check(lib.ital_select_fused(_ptr(mi), _ptr(cand_d), _ptr(alive), n_loc, pos_offset, _ptr(gpos_d), gp.row0,
-                                                gp.rank, 0, _ptr(gp.mu), _ptr(gp.s2), _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx,
-                                                _ptr(gp.V), gp.ldv, gp.m, gp.cap, _ptr(b["C"]), gp.ldv, t - 1, t - 1, b["batch"],
-                                                _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]), st))
-                else:
-                    if not tail:
-                        check(lib.ital_select_local(_ptr(mi), _ptr(cand_d), _ptr(alive), n_loc, pos_offset, _ptr(gpos_d), gp.row0,
-                                                    gp.rank, 0, _ptr(gp.mu), _ptr(gp.s2), _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx,
-                                                    _ptr(gp.V), gp.ldv, gp.m, gp.cap, _ptr(b["C"]), gp.ldv, t - 1, b["kmax"],
-                                                    _ptr(gp.status), _ptr(b["work"]), _ptr(b["rec"]), st))
-                    if gp.collective:
-                        ev0 = self._mark()
-                        recs = sharding.gather_records(b["rec"], b["rec_all"], gp.group)
-                        self._mark("exchange", t, gp.world, ev0)
-                    else:
-                        recs = b["rec"]
-                    check(lib.ital_select_resolve(_ptr(recs), gp.world, b["rec_len"], gp.rank, 0, t - 1, b["batch"],
-                                                  _ptr(alive), _ptr(b["ret"]), st))
+                if not (tail and fused):
+                    select_step(gp, b, scored, gp_model(gp), t - 1, st, fused=fused, local=not tail, mark=self._mark)
                 if t < k:
-                    slot = t - 1
                     ev0 = self._mark() if t == 1 else None           # one sample of the streaming kernel per round
-                    check(lib.ital_cross_cov_cols(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(b["XB"][slot]),
-                                                  _ptr(b["XBn"][slot:]), 1, _ptr(b["VB"][slot]), gp.cap, _ptr(gp.V),
-                                                  gp.ldv, gp.m, float(self.var), float(self.length_scale),
-                                                  _ptr(b["C"][slot]), gp.ldv, st))
+                    member_column(self, gp_model(gp), b, t - 1, st)
                     if t == 1:
                         self._mark("cross_cov", t, gp.m, ev0)
                 # the reference's serial loop has now consumed this many uniforms of mvndst's stream
@@ -517,7 +460,7 @@ class ITAL(ActiveRetrievalBase):
                 float(self.var), float(self.length_scale), self.label_estimation, self.qmc_work_bytes,
                 self.profile is not None, repr(self.profile_steps))
 
-    def _round_prepare(self, slot, b, k, n, m, begin, cur, state_before, n_prev=0, n_loc=None, pos_offset=0):
+    def _round_prepare(self, slot, b, k, n, m, begin, cur, state_before, *, n_prev=0, n_loc=None, pos_offset=0):
         """Fills round descriptor `slot` (one of two) for a round of k steps over n candidates with m labelled samples, the
         candidate list in device buffer `cur` (begin = 2: compacted out of the other buffer, which holds n_prev entries).
         Several ranks: n_loc of the n candidates are this rank's, the first of them at list position pos_offset.
@@ -532,9 +475,7 @@ class ITAL(ActiveRetrievalBase):
         r.k, r.n_rows, r.var, r.length_scale = k, gp.n, float(self.var), float(self.length_scale)
         r.begin, r.cand_prev, r.n_prev = begin, (_ptr(lists[cur ^ 1]) if begin == 2 else None), (n_prev if begin == 2 else 0)
         n_loc = n if n_loc is None else n_loc
-        d.n_cand = n_loc
-        d.cand, d.alive, d.mu, d.s2 = _ptr(lists[cur]), _ptr(b["alive"]), _ptr(gp.mu), _ptr(gp.s2)
-        d.C, d.ldc, d.row_offset, d.pos_offset, d.gpos = _ptr(b["C"]), gp.ldv, gp.row0, pos_offset, None
+        fill_score_desc(d, gp, b, Scored(b["mi"], lists[cur], b["alive"], n_loc, pos_offset, None, gp.row0), self._user())
         r.world, r.records_all, r.nccl_comm, r.exchange = 0, None, None, _lib.EXCHANGE_FN(0)
         if gp.collective:
             kind, comm = self._round_transport()
@@ -543,14 +484,7 @@ class ITAL(ActiveRetrievalBase):
                 r.nccl_comm = comm
             else:
                 r.exchange = self._host_exchange(b)
-        d.batch = b["batch"]
-        d.noise, d.eps, d.label_mode = float(self.noise), float(self.eps), _LABEL_MODES[self.label_estimation]
-        d.mi, d.status = _ptr(b["mi"]), _ptr(gp.status)
-        d.sel_X, d.sel_xnorm, d.sel_ldx = _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx
-        d.sel_V, d.sel_ldv, d.sel_m, d.sel_ldw, d.sel_rank = _ptr(gp.V), gp.ldv, m, gp.cap, gp.rank
-        d.sel_record, d.sel_ret = _ptr(b["rec"]), _ptr(b["ret"])
-        parts = b["sel_parts"]
-        d.sel_parts, d.sel_parts_len, d.sel_counter = _ptr(parts), parts.numel(), _ptr(b["sel_counter"])
+        fill_score_select(d, gp, b, m, b["ret"])
         r.mi_keep = None
         events = []
         if k >= 3:
@@ -559,11 +493,7 @@ class ITAL(ActiveRetrievalBase):
         for t in range(1, k + 1):
             r.ev_start[t] = r.ev_stop[t] = None
             if t >= 3:
-                if t not in b["jump"]:
-                    b["jump"][t] = torch.from_numpy(mvn_stream.jump_table(t, ITAL_JUMP_BITS)).to(dev)
-                    b["jumppat"][t] = torch.from_numpy(mvn_stream.jump_pattern_table(t)).to(dev)
-                    b["vk"][t] = torch.from_numpy(mvn_stream.korobov_vk(t)).to(dev)
-                r.jump[t], r.jumppat[t], r.vk[t] = _ptr(b["jump"][t]), _ptr(b["jumppat"][t]), _ptr(b["vk"][t])
+                r.jump[t], r.jumppat[t], r.vk[t] = [_ptr(x) for x in lattice_tables(b, t, dev)]
                 if self.profile is not None and (self.profile_steps is None or t in self.profile_steps):
                     k0, k1 = self._event(), self._event()
                     r.ev_start[t], r.ev_stop[t] = k0.cuda_event, k1.cuda_event
@@ -645,7 +575,8 @@ class ITAL(ActiveRetrievalBase):
                     begin = 1
                     share = candidates.in_rows(gp.row0, gp.row1) if listed else np.asarray(candidates, dtype=np.int64)
                     lists[b["cand_cur"]][:n_loc].copy_(torch.from_numpy((share - gp.row0).astype(np.int32)))
-                p = self._round_prepare(0, b, k, n, gp.m, begin, b["cand_cur"], stream.state, n_prev, n_loc, lo)
+                p = self._round_prepare(0, b, k, n, gp.m, begin, b["cand_cur"], stream.state, n_prev=n_prev, n_loc=n_loc,
+                                        pos_offset=lo)
             b["round_next"] = None
             self.last_round = (p["begin"], p["slot"])          # diagnostics / tests: how the candidate list reached the device
             r = b["round_descs"][p["slot"]]
@@ -676,7 +607,7 @@ class ITAL(ActiveRetrievalBase):
             if n - k >= k and gp.m + k <= gp.cap and not self.keep_scores:
                 # (several ranks: this rank's share of that list is known only with the picks -- patched in when the round comes)
                 b["round_next"] = self._round_prepare(p["slot"] ^ 1, b, k, n - k, gp.m + k, 2, b["cand_cur"] ^ 1, stream.state,
-                                                      n_loc, n_loc if gp.collective else n - k, lo)
+                                                      n_prev=n_loc, n_loc=n_loc if gp.collective else n - k, pos_offset=lo)
             if hc is not None:
                 hc["enqueue_s"] += time.perf_counter() - t_call     # the call itself + the next round's descriptor (GPU busy)
             host = self._download(b["ret"], "the picks of the round", self._step_estimate_s(k, n_loc)).tolist()     # the only synchronisation of the round: the picks and the status word
@@ -701,534 +632,8 @@ class ITAL(ActiveRetrievalBase):
     # ------------------------------------------------------------------ general scorer (noisy users, estimation subset)
     def _fetch_generic(self, k, candidates):
         """Greedy batch construction through ital_score_generic: any user model (reference ital.py:300-342), with or
-        without a change-estimation subset (ital.py:227-275, 541-582).
-
-        Without a subset the base set of the scorer IS the batch so far: it lives in the replicated device batch state that
-        ital_select_resolve / ital_select_fused maintain, and a round is enqueued without any host round trip (one download
-        of the picks at the end) unless an option needs the host between the steps (Monte-Carlo sampling on numpy's
-        generator, the counting pass of clip_cov).  With a subset the base set also holds the subset members and grows only
-        when a pick lies outside it: that bookkeeping stays on the host (one synchronisation per greedy step)."""
-        lib = _lib.lib()
-        gp = self.gp
-        dev = gp.device
+        without a change-estimation subset (ital.py:227-275, 541-582), the Monte-Carlo switches, clip_cov, label
+        estimation; also every fallback of the fast paths.  The round itself is _generic_round.GenericRound."""
         self._last_batch = None
-        subset_mode = self._ce_subset is not None
-        fb_mode = self._fb_mode()
-        E = list(self._ce_subset) if subset_mode else []
-        kmax_e = len(E) + k
-        GN = ITAL_GENERIC_MAX_DIM
-        stream = mvn_stream.GLOBAL
-        h = ITAL_REC_HEADER
-        with torch.cuda.device(dev):
-            st = _stream()
-            b = self._buffers(max(kmax_e, 4))
-            kmax = b["kmax"]
-            cand, n_loc, pos_offset, cand_d, gpos_d, alive = self._shard(candidates)
-            # every rank's candidates one contiguous run of the list (the ascending get_unseen() order; not after the
-            # argpartition order of top_candidates on several ranks)?  Decided from the list alone: the same on every rank
-            runs = sharding.contiguous_runs(cand, gp.n_total, gp.world, self._ascending(candidates))
-            pos_of = {int(c): i for i, c in enumerate(cand.tolist())}
-            mi = torch.zeros(max(n_loc, 1), dtype=torch.float64, device=dev)
-            if "jump1" not in b:
-                b["jump1"] = torch.from_numpy(mvn_stream.jump1_table(ITAL_JUMP_BITS)).to(dev)
-                b["vk_all"] = torch.from_numpy(mvn_stream.vk_table(GN)).to(dev)
-                b["iota"] = torch.arange(kmax, dtype=torch.int32, device=dev)
-                b["zero64"] = torch.zeros(1, dtype=torch.int64, device=dev)
-            jump1, vk = b["jump1"], b["vk_all"]
-            C = b["C"]
-            e_mu = np.zeros(kmax_e)
-            e_sig = np.zeros((kmax_e, kmax_e))
-            keep = []                     # device temporaries of the enqueued work (released after the round's synchronisation)
-            b["ret"][kmax:].zero_()
-            if E:
-                # covariance columns of the subset members with every row, and among themselves
-                rows = gp._gather_rows(E)
-                norms = torch.empty(len(E), dtype=torch.float64, device=dev)
-                check(lib.ital_row_norms(_ptr(rows), len(E), gp.ldx, _ptr(norms), st))
-                vcols = gp.gather_columns(gp.V[: max(gp.m, 1)], E)          # [m, |E|]
-                for c0 in range(0, len(E), 16):
-                    c = min(16, len(E) - c0)
-                    Wt = torch.zeros((c, gp.cap), dtype=torch.float64, device=dev)
-                    Wt[:, : gp.m] = vcols[: gp.m, c0:c0 + c].t()
-                    check(lib.ital_cross_cov_cols(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(rows[c0:c0 + c]),
-                                                  _ptr(norms[c0:c0 + c]), c, _ptr(Wt), gp.cap, _ptr(gp.V), gp.ldv, gp.m,
-                                                  float(self.var), float(self.length_scale), _ptr(C[c0:c0 + c]), gp.ldv,
-                                                  st))
-                    keep.append(Wt)
-                keep += [rows, norms, vcols]
-                e_sig[: len(E), : len(E)] = gp.gather_columns(C[: len(E)], E).cpu().numpy()
-                e_mu[: len(E)] = self.rel_mean[np.asarray(E)]
-            picks, pick_pos = [], []
-            self._mc_cache = {}           # host copies of this rank's variances / covariance columns (pattern sampling)
-            self.last_scores = []
-            self.last_patterns = []       # keep_scores: the sampled sign patterns of every Monte-Carlo step (diagnostics/tests)
-            n_alive = len(candidates)
-            z_next = None
-            for t in range(1, k + 1):
-                nE = len(E) if subset_mode else t - 1
-                nr = t
-                rel_mc, npat, fb_mc, nfb = self._mc_plan(nr, fb_mode)
-                clip_count = self._clip_active() and nE + 1 > 5
-                dpc = mvn_stream.draws_per_call
-                if subset_mode:
-                    draws_out = npat * (dpc(nr) + (1 + nfb) * dpc(nE + 1))
-                    draws_in = npat * (dpc(nr) + (1 + nfb) * dpc(nE))
-                    in_pos = sorted(pos_of[e] for e in E if e in pos_of and e not in picks)
-                else:
-                    draws_out = npat * (1 + nfb) * dpc(nr)
-                    draws_in = 0
-                    in_pos = []
-                mc = None
-                if rel_mc or fb_mc:
-                    t_host0 = time.perf_counter()
-                    if not subset_mode and t > 1:
-                        # batch state kept by the device: the members' means / covariances for the pattern sampler
-                        picks = [int(i) for i in b["ret"][: t - 1].cpu().tolist()]
-                        t_host1 = time.perf_counter()          # (the wait for the step before: GPU time, not host time)
-                        pick_pos = list(range(t - 1))
-                        e_mu[: t - 1] = b["bmu"][: t - 1].cpu().numpy()
-                        e_sig[: t - 1, : t - 1] = b["sig"].view(kmax, kmax)[: t - 1, : t - 1].cpu().numpy()
-                    else:
-                        t_host1 = t_host0
-                    # pattern sampling alone on a large shard: the step is scored in ranges of candidates, the SVDs of the
-                    # next range on the host under the lattice sums of the current one
-                    n_chunks = (_MC_CHUNKS + (2 if n_loc >= 32 * _MC_CHUNK_MIN else 0)) if (rel_mc and not fb_mc and not subset_mode and not clip_count and runs
-                                              and gpos_d is None
-                                              and (nr >= _MC_CHUNK_FROM or (nr >= 7 and n_loc >= 32 * _MC_CHUNK_MIN))
-                                              and n_loc >= _MC_CHUNK_MIN * _MC_CHUNKS) else 0
-                    mc = self._mc_samples(nr, npat, rel_mc, fb_mc, nfb, fb_mode, cand, picks, pos_of,
-                                          E if subset_mode else picks, pick_pos, e_mu, e_sig, C, subset_mode, z_next,
-                                          (pos_offset, pos_offset + n_loc) if runs else None, n_chunks)
-                    if os.environ.get("ITAL_MC_TIMING"):
-                        print("t=%d: waited %.1f ms for the step before; batch state + sampler set-up%s %.1f ms" % (
-                            t, (t_host1 - t_host0) * 1e3, "" if n_chunks else " + ALL decompositions",
-                            (time.perf_counter() - t_host1) * 1e3), flush=True)
-                z_next = None
-                desc = ItalGscoreDesc()
-                desc.n_cand = n_loc
-                desc.cand, desc.alive, desc.mu, desc.s2 = _ptr(cand_d), _ptr(alive), _ptr(gp.mu), _ptr(gp.s2)
-                desc.C, desc.ldc = _ptr(C), gp.ldv
-                desc.row_offset, desc.pos_offset, desc.gpos = gp.row0, pos_offset, _ptr(gpos_d)
-                if subset_mode:
-                    dead_pos = [pos_of[q] for q in picks]
-                    t_eidx = torch.as_tensor(E if E else [0], dtype=torch.int64, device=dev)
-                    t_esort = torch.as_tensor(np.argsort(np.asarray(E, dtype=np.int64), kind="stable") if E else [0],
-                                              dtype=torch.int32, device=dev)
-                    t_emu = torch.from_numpy(np.ascontiguousarray(e_mu)).to(dev)
-                    t_esig = torch.from_numpy(np.ascontiguousarray(e_sig)).to(dev)
-                    t_ppos = torch.as_tensor(pick_pos if pick_pos else [0], dtype=torch.int32, device=dev)
-                    t_in = torch.as_tensor(in_pos if in_pos else [0], dtype=torch.int64, device=dev)
-                    t_dead = torch.as_tensor(dead_pos if dead_pos else [0], dtype=torch.int64, device=dev)
-                    keep += [t_eidx, t_esort, t_emu, t_esig, t_ppos, t_in, t_dead]
-                    desc.nE, desc.E_idx, desc.E_sort, desc.E_mu, desc.E_sig, desc.ldE = nE, _ptr(t_eidx), _ptr(t_esort), \
-                        _ptr(t_emu), _ptr(t_esig), kmax_e
-                    desc.n_picks, desc.pick_pos = len(picks), _ptr(t_ppos)
-                    desc.n_in, desc.in_pos, desc.n_dead, desc.dead_pos = len(in_pos), _ptr(t_in), len(dead_pos), _ptr(t_dead)
-                else:
-                    # the base set is the batch so far: members, their order by data index, means, covariances and list
-                    # positions are the device batch state itself
-                    desc.nE, desc.E_idx, desc.E_sort, desc.E_mu, desc.E_sig, desc.ldE = nE, _ptr(b["bidx"]), \
-                        _ptr(b["bsort"]), _ptr(b["bmu"]), _ptr(b["sig"]), kmax
-                    desc.n_picks, desc.pick_pos = nE, _ptr(b["iota"])
-                    desc.n_in, desc.in_pos, desc.n_dead, desc.dead_pos = 0, _ptr(b["zero64"]), nE, _ptr(b["bgpos"])
-                desc.subset_mode, desc.fb_mode = int(subset_mode), fb_mode
-                desc.label_prob, desc.mistake_prob = float(self.label_prob), float(self.mistake_prob)
-                desc.label_mode = _LABEL_MODES[self.label_estimation]
-                desc.noise, desc.eps = float(self.noise), float(self.eps)
-                desc.clip_cov = float(self.clip_cov) if self._clip_active() else 0.0
-                for j in range(6):
-                    desc.seed[j] = stream.state[j]
-                desc.jump1, desc.vk = _ptr(jump1), _ptr(vk)
-                desc.draws_out, desc.draws_in = draws_out, draws_in
-                desc.mi, desc.status = _ptr(mi), _ptr(gp.status)
-                desc.pair_count = _ptr(self.pair_counter)
-                if self.generic_pipeline and not self._clip_active() and nE + 1 <= (13 if subset_mode else 16):
-                    # (round 5: with a change-estimation subset too -- the pipeline's wide form, one lattice-sum launch per
-                    # dimension that occurs among the step's calls)
-                    # workspace of the pipeline of kernels (verdicts, records of the calls to integrate): what one slab of
-                    # all candidates takes, capped (the library then walks the candidates in several slabs)
-                    desc.mc_rel, desc.mc_fb = (npat if rel_mc else 0), (nfb if fb_mc else 0)     # (read by the size query)
-                    want = int(lib.ital_score_generic_workspace(ctypes.byref(desc)))
-                    desc.mc_rel, desc.mc_fb = 0, 0
-                    want = min(want, max(self.qmc_work_bytes // 8, 1 << 16))
-                    w = b.get("qmc_work")
-                    if w is None or w.numel() < want:
-                        b["qmc_work"] = w = torch.empty(want, dtype=torch.float64, device=dev)
-                    desc.work, desc.work_doubles = _ptr(w), w.numel()
-                total_draws = None
-                rel_ranges = None
-                if mc is None and self.keep_scores:
-                    self.last_patterns.append(None)          # this step enumerates its patterns
-                if mc is not None:
-                    rel_arr, fb_arr, draws_pp = mc          # per list position (dead positions hold zeros)
-                    if rel_arr is not None and not isinstance(rel_arr, np.ndarray):
-                        rel_ranges, rel_arr = rel_arr, None     # generator of (lo, hi, rows): consumed at the launches below
-                    if self.keep_scores and rel_ranges is None:
-                        self.last_patterns.append(rel_arr)
-                    if gpos_d is None:
-                        mine = slice(pos_offset, pos_offset + max(n_loc, 1))
-                    else:
-                        mine = gpos_d.cpu().numpy()
-                    if rel_arr is not None:
-                        t_rel = torch.from_numpy(np.ascontiguousarray(rel_arr[mine])).to(dev)
-                        desc.mc_rel, desc.rel_samples = npat, _ptr(t_rel)
-                        keep.append(t_rel)
-                    if fb_arr is not None:
-                        t_fb = torch.from_numpy(np.ascontiguousarray(fb_arr[mine])).to(dev)
-                        desc.mc_fb, desc.fb_samples = nfb, _ptr(t_fb)
-                        keep.append(t_fb)
-                    off = np.concatenate(([0], np.cumsum(draws_pp)[:-1])).astype(np.int64)
-                    t_off = torch.from_numpy(np.ascontiguousarray(off[mine])).to(dev)
-                    keep.append(t_off)
-                    desc.draw_off = _ptr(t_off)
-                    total_draws = int(draws_pp.sum())
-                if clip_count:
-                    # with clip_cov the number of mvndst calls (one per group of correlated variables) and hence the
-                    # stream consumption depends on the data: a counting pass of the same kernel reports it per candidate
-                    counts = torch.zeros(max(n_loc, 1), dtype=torch.int64, device=dev)
-                    desc.draw_count = _ptr(counts)
-                    check(lib.ital_score_generic(ctypes.byref(desc), st))
-                    desc.draw_count = None
-                    if gp.collective:
-                        # uniforms consumed before each of this rank's candidates: prefix over the whole list
-                        full = torch.zeros(len(cand), dtype=torch.int64, device=dev)
-                        if n_loc:
-                            if gpos_d is None:
-                                full[pos_offset:pos_offset + n_loc] = counts[:n_loc]
-                            else:
-                                full[gpos_d] = counts[:n_loc]
-                        sharding.all_reduce_sum(full, gp.group)
-                        excl = torch.cumsum(full, 0) - full
-                        t_off = (excl[pos_offset:pos_offset + max(n_loc, 1)] if gpos_d is None else excl[gpos_d]).contiguous()
-                        total_draws = int(full.sum().item())
-                    else:
-                        t_off = torch.cumsum(counts, 0) - counts
-                        total_draws = int(counts.sum().item())
-                    keep += [counts, t_off]
-                    desc.draw_off = _ptr(t_off)
-                ev0 = self._mark()
-                if rel_ranges is None:
-                    check(lib.ital_score_generic(ctypes.byref(desc), st))
-                else:
-                    # one call per range of candidates: patterns of range r + 1 are decomposed on the host (LAPACK, thread
-                    # pool) while the GPU integrates range r; the uploads go through page-locked memory on a stream of
-                    # their own (a pageable copy would wait for the scorer in front of it)
-                    if b.get("mc_pin") is None or b["mc_pin"].shape[0] < n_loc or b["mc_pin"].shape[1] < npat:
-                        b["mc_pin"] = torch.empty((n_loc, ITAL_GENERIC_MAX_REL), dtype=torch.int32).pin_memory()
-                        b["mc_dev"] = torch.empty((n_loc, ITAL_GENERIC_MAX_REL), dtype=torch.int32, device=dev)
-                        b["mc_stream"] = torch.cuda.Stream(device=dev)
-                    pin, t_rel, side = b["mc_pin"], b["mc_dev"], b["mc_stream"]
-                    main = torch.cuda.current_stream(dev)
-                    side.wait_stream(main)                   # earlier readers of the device buffer (the step before) are done
-                    kept = np.zeros((len(cand), npat), dtype=np.uint32) if self.keep_scores else None
-                    base = {f: getattr(desc, f) for f in ("cand", "alive", "mi", "draw_off", "pos_offset")}
-                    dbg = os.environ.get("ITAL_MC_TIMING")
-                    tq = time.perf_counter()
-                    # (try / finally around the WHOLE loop, not only the C call: the generator runs host LAPACK and thread-pool
-                    # work between the ranges -- if that raises while a deferred range is still running on the library's internal
-                    # streams, the join below is what orders those kernels, which write `mi` and the workspace, before anything
-                    # the caller's stream does next with these torch buffers)
-                    try:
-                        for lo, hi, rows, last_range in rel_ranges:
-                            if dbg:
-                                t_rows = time.perf_counter() - tq
-                                tq = time.perf_counter()
-                            a, e = lo - pos_offset, hi - pos_offset
-                            flat = pin.view(-1)[a * npat:e * npat]
-                            flat.copy_(torch.from_numpy(rows.view(np.int32).reshape(-1)))
-                            dflat = t_rel.view(-1)[a * npat:e * npat]
-                            with torch.cuda.stream(side):
-                                dflat.copy_(flat, non_blocking=True)
-                            up = torch.cuda.Event()
-                            up.record(side)
-                            main.wait_event(up)
-                            desc.n_cand = e - a
-                            desc.cand, desc.alive = base["cand"] + 4 * a, base["alive"] + a
-                            desc.mi, desc.draw_off = base["mi"] + 8 * a, base["draw_off"] + 8 * a
-                            desc.pos_offset = base["pos_offset"] + a
-                            desc.mc_rel, desc.rel_samples = npat, dflat.data_ptr()
-                            # all but the last range leave the library's streams unjoined: the preparation of the next range's
-                            # first slab then runs under this range's lattice sums (ital_gscore_desc.defer_join)
-                            desc.defer_join = 0 if last_range else 1
-                            check(lib.ital_score_generic(ctypes.byref(desc), st))
-                            if dbg:
-                                print("t=%d range %d..%d: patterns %.1f ms, upload + launch %.1f ms" % (
-                                    t, lo, hi, t_rows * 1e3, (time.perf_counter() - tq) * 1e3), flush=True)
-                                tq = time.perf_counter()
-                            if kept is not None:
-                                kept[lo:hi] = rows
-                    finally:
-                        desc.defer_join = 0
-                        rc_join = lib.ital_score_generic_join(st)      # (nothing pending after a last range; cheap)
-                    check(rc_join)
-                    if kept is not None:
-                        self.last_patterns.append(kept)
-                self._mark("score_generic", t, n_alive, ev0)
-                if self.keep_scores:
-                    self.last_scores.append(mi.clone())
-                n_in_alive = len(in_pos)
-                stream.advance(total_draws if total_draws is not None else
-                               (n_alive - n_in_alive) * draws_out + n_in_alive * draws_in)
-                n_alive -= 1
-                if t < k:
-                    # the standard normals of the next step's pattern sampling depend on nothing but their count: drawn
-                    # now, while the scorer runs, they are off the critical path (same order on numpy's global generator).
-                    # Only this rank's candidates' normals are computed; the generator is walked past the others'
-                    # (ital_np_legacy_normals).  The next step's live ranks of the local positions [lo, hi) depend on the
-                    # pick this step is about to make: lo - t <= first, last <= hi covers every outcome
-                    rel_nx, npat_nx, fb_nx, _ = self._mc_plan(nr + 1, fb_mode)
-                    if rel_nx and not fb_nx:
-                        g0, g1 = (0, n_alive) if not runs else \
-                            (max(pos_offset - t, 0), min(pos_offset + n_loc, n_alive))
-                        z_next = (g0, self._walk_normals(n_alive, g0, g1, npat_nx * (nr + 1)).reshape(-1, npat_nx, nr + 1))
-                if not subset_mode:
-                    slot = t - 1
-                    if not gp.collective and n_loc <= _FUSED_LAUNCH_MAX:
-                        check(lib.ital_select_fused(_ptr(mi), _ptr(cand_d), _ptr(alive), n_loc, pos_offset, _ptr(gpos_d),
-                                                    gp.row0, gp.rank, 0, _ptr(gp.mu), _ptr(gp.s2), _ptr(gp.Xd),
-                                                    _ptr(gp.xnorm), gp.ldx, _ptr(gp.V), gp.ldv, gp.m, gp.cap, _ptr(C), gp.ldv,
-                                                    slot, slot, b["batch"], _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]),
-                                                    st))
-                    else:
-                        check(lib.ital_select_local(_ptr(mi), _ptr(cand_d), _ptr(alive), n_loc, pos_offset, _ptr(gpos_d),
-                                                    gp.row0, gp.rank, 0, _ptr(gp.mu), _ptr(gp.s2), _ptr(gp.Xd),
-                                                    _ptr(gp.xnorm), gp.ldx, _ptr(gp.V), gp.ldv, gp.m, gp.cap, _ptr(C), gp.ldv,
-                                                    slot, kmax, _ptr(gp.status), _ptr(b["work"]), _ptr(b["rec"]), st))
-                        recs = sharding.gather_records(b["rec"], b["rec_all"], gp.group) if gp.collective else b["rec"]
-                        check(lib.ital_select_resolve(_ptr(recs), gp.world, b["rec_len"], gp.rank, 0, slot, b["batch"],
-                                                      _ptr(alive), _ptr(b["ret"]), st))
-                    if t < k:
-                        ev0 = self._mark()
-                        check(lib.ital_cross_cov_cols(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(b["XB"][slot]),
-                                                      _ptr(b["XBn"][slot:]), 1, _ptr(b["VB"][slot]), gp.cap, _ptr(gp.V),
-                                                      gp.ldv, gp.m, float(self.var), float(self.length_scale),
-                                                      _ptr(C[slot]), gp.ldv, st))
-                        self._mark("cross_cov", t, gp.m, ev0)
-                    continue
-                # ---- subset mode: the winner is resolved on the host (it may or may not extend the base set)
-                check(lib.ital_select_local(_ptr(mi), _ptr(cand_d), _ptr(alive), n_loc, pos_offset, _ptr(gpos_d), gp.row0,
-                                            gp.rank, 0, _ptr(gp.mu), _ptr(gp.s2), _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx,
-                                            _ptr(gp.V), gp.ldv, gp.m, gp.cap, _ptr(C), gp.ldv, nE, kmax, _ptr(gp.status),
-                                            _ptr(b["work"]), _ptr(b["rec"]), st))
-                recs = sharding.gather_records(b["rec"], b["rec_all"], gp.group) if gp.collective else b["rec"].unsqueeze(0)
-                recs_h = self._download(recs, "the records of greedy step %d" % t).numpy()          # host synchronisation of this greedy step
-                keep.clear()
-                w = sharding.winner(recs_h, 0)
-                rec = recs_h[w]
-                pick = int(rec[2])
-                if int(rec[6]) == gp.rank:
-                    alive[int(rec[7])] = 0
-                picks.append(pick)
-                if pick in E:
-                    pick_pos.append(E.index(pick))
-                else:
-                    # new member of the base set: its covariance column, mean and covariances with the members so far
-                    e_mu[nE] = rec[3]
-                    e_sig[nE, nE] = rec[4]
-                    e_sig[nE, :nE] = rec[h + gp.ldx + gp.cap: h + gp.ldx + gp.cap + nE]
-                    e_sig[:nE, nE] = e_sig[nE, :nE]
-                    if t < k:
-                        rec_d = recs[w]
-                        xrow = rec_d[h:h + gp.ldx].contiguous()
-                        vcol = rec_d[h + gp.ldx:h + gp.ldx + gp.cap].contiguous()
-                        xn = rec_d[5:6].contiguous()
-                        check(lib.ital_cross_cov_cols(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(xrow), _ptr(xn), 1,
-                                                      _ptr(vcol), gp.cap, _ptr(gp.V), gp.ldv, gp.m, float(self.var),
-                                                      float(self.length_scale), _ptr(C[nE]), gp.ldv, st))
-                        keep += [xrow, vcol, xn]
-                    pick_pos.append(nE)
-                    E.append(pick)
-            if not subset_mode:
-                host = self._download(b["ret"], "the picks of the round").tolist()        # picks and the status word (OR over steps and ranks)
-                picks, status = host[:k], host[kmax]
-            else:
-                status = None                         # only the replicated Cholesky append reports here: same on all ranks
-            keep.clear()
-        gp.check_status(status)
-        if not subset_mode:
-            self._last_batch = (b, [int(i) for i in picks])
-        return [int(i) for i in picks]
-
-    def _walk_normals(self, n_live, j0, j1, per_cand):
-        """numpy's global generator walked over the `per_cand` standard normals of each of `n_live` candidates
-        (multivariate_normal.rvs per candidate, reference ital.py:297); returns those of candidates j0 .. j1-1 (flat).
-        `mc_walk` accumulates [normals computed, normals skipped, seconds] (diagnostics / tests)."""
-        j0, j1 = max(int(j0), 0), min(int(j1), int(n_live))
-        j1 = max(j1, j0)
-        t0 = time.perf_counter()
-        z = _lib.legacy_normals(j0 * per_cand, (j1 - j0) * per_cand, _HOST_THREADS)
-        _lib.legacy_normals((n_live - j1) * per_cand, 0)
-        self.mc_walk[0] += (j1 - j0) * per_cand
-        self.mc_walk[1] += (n_live - (j1 - j0)) * per_cand
-        self.mc_walk[2] += time.perf_counter() - t0
-        return z
-
-    def _mc_samples(self, nr, npat, rel_mc, fb_mc, nfb, fb_mode, cand, picks, pos_of, E, pick_pos, e_mu, e_sig, C, subset_mode,
-                    z_rel=None, local=None, chunks=0):
-        """Sign patterns / feedback configurations of the Monte-Carlo switches, drawn from numpy's global RNG in the
-        reference's serial order (per live candidate: one multivariate_normal.rvs, ital.py:297; per pattern one
-        np.random.choice, ital.py:323-337).  `z_rel`: the standard normals of this step when the caller drew them ahead
-        (pattern sampling only); `local`: list positions [lo, hi) whose patterns this rank reads.  Returns per list position: patterns [P, npat] uint32 (or None), feedback
-        [P, npat, nfb] uint32 (or None), uniforms of mvndst's stream consumed [P] int64.
-        `chunks` > 0 (pattern sampling alone, `local` given): the patterns come back as a generator of (lo, hi, rows) over
-        `chunks` consecutive ranges of the local list positions -- the per-candidate decompositions of a range are only done
-        when it is asked for, so the caller can score one range on the GPU while the host prepares the next."""
-        gp = self.gp
-        P = len(cand)
-        dead = np.zeros(P, dtype=bool)
-        for q in picks:
-            dead[pos_of[q]] = True
-        live = np.flatnonzero(~dead)
-        nE = len(E)
-        in_e = np.full(P, -1, dtype=np.int64)
-        if subset_mode:
-            for e_pos, e in enumerate(E):
-                if e in pos_of:
-                    in_e[pos_of[e]] = e_pos
-        n_full = np.where(in_e >= 0, nE, nE + 1)               # orthant dimension of the full-dimension calls
-        dpc = mvn_stream.draws_per_call
-        d_full = np.array([dpc(int(v)) for v in range(nE + 2)], dtype=np.int64)[n_full]
-        npre_draws = (dpc(nr) + d_full) if subset_mode else d_full
-        rel_arr = fb_arr = None
-        # ---- mean / covariance of the enumerated variables of the live candidates (ital.py:247-248, :529); with pattern
-        # sampling alone only of the ones this rank scores (live[jl0:jl1]): nobody reads the other patterns
-        jl0, jl1 = 0, len(live)
-        if rel_mc and not fb_mc and local is not None:
-            jl0, jl1 = int(np.searchsorted(live, local[0])), int(np.searchsorted(live, local[1]))
-        if rel_mc:
-            mu_all = np.asarray(self.rel_mean, dtype=np.float64)
-            pp = list(pick_pos)
-            rows = cand[live[jl0:jl1]]
-            cache = self._mc_cache
-            if rel_mc and not fb_mc and local is not None:
-                # (the same decision on every rank: `local` is set for all of them or for none)
-                # every row read below is a row of this rank: variances and covariance columns come from the local shard
-                # (a column is downloaded once per fetch, when its member joins the batch) -- no collective, nothing N-sized
-                if "s2" not in cache:
-                    cache["s2"] = gp.s2[: gp.n].cpu().numpy()
-                for b in pp:
-                    if ("C", b) not in cache:
-                        cache[("C", b)] = C[b][: gp.n].cpu().numpy()
-                s2_all, rows_l = cache["s2"], rows - gp.row0
-                cpick = np.stack([cache[("C", b)] for b in pp]) if pp else np.zeros((0, gp.n))
-            else:
-                s2_all, rows_l = gp._full(gp.s2), rows
-                cpick = np.stack([gp._full(C[b]) for b in pp]) if pp else np.zeros((0, gp.n_total))
-
-            def moments(j0, j1):
-                """Mean [n, nr] and covariance [n, nr, nr] of (members so far, candidate) for live candidates j0 .. j1-1."""
-                rw, rl = rows[j0 - jl0:j1 - jl0], rows_l[j0 - jl0:j1 - jl0]
-                mean = np.empty((len(rw), nr))
-                cov = np.empty((len(rw), nr, nr))
-                mean[:, : nr - 1] = e_mu[pp][None, :] if pp else 0
-                cov[:, : nr - 1, : nr - 1] = e_sig[np.ix_(pp, pp)][None] if pp else 0
-                mean[:, nr - 1] = mu_all[rw]
-                cov[:, nr - 1, nr - 1] = s2_all[rl]
-                if pp:
-                    cov[:, : nr - 1, nr - 1] = cpick[:, rl].T
-                    cov[:, nr - 1, : nr - 1] = cov[:, : nr - 1, nr - 1]
-                if subset_mode:
-                    for j in np.flatnonzero(in_e[live[j0:j1]] >= 0):    # members of the base set: covariances from E itself
-                        idx = pp + [int(in_e[live[j0 + j]])]
-                        mean[j] = e_mu[idx]
-                        cov[j] = e_sig[np.ix_(idx, idx)]
-                elif nr == 1:
-                    cov[:, 0, 0] = np.maximum(0, cov[:, 0, 0])     # first step: predict_stored(cov_mode='diag') (ital.py:558)
-                return mean, cov
-        weights = (1 << np.arange(nr - 1, -1, -1)).astype(np.uint32)   # variable v at bit nr-1-v
-        if fb_mc:
-            if fb_mode == 1:
-                vals = np.array([1, -1])
-                pr = np.array([1.0 - self.mistake_prob, self.mistake_prob])
-            else:
-                vals = np.array([0, 1, -1])
-                pr = np.array([1.0 - self.label_prob, self.label_prob * (1.0 - self.mistake_prob),
-                               self.label_prob * self.mistake_prob])
-            cdf = pr.cumsum()
-            cdf /= cdf[-1]
-
-        def transform(z, j0, j1):
-            mean, cov = moments(j0, j1)
-            _, sv, vt = np.linalg.svd(cov)
-            x = z @ (np.sqrt(sv)[:, :, None] * vt) + mean[:, None, :]
-            return ((x > 0) * weights).sum(axis=2).astype(np.uint32)
-
-        def draw_rel(j0, j1, z=None):
-            """multivariate_normal.rvs for live candidates j0..j1-1: numpy's legacy generator = standard normals in
-            order, then x = z . (sqrt(s) v) + mean with (u, s, v) = svd(cov).  The per-candidate LAPACK calls are
-            independent of each other: large stacks are cut into slices for a thread pool (numpy's gufuncs release the
-            GIL; the result is the same bits as one call)."""
-            if z is None:
-                z = np.random.standard_normal((j1 - j0, npat, nr))
-            n = j1 - j0
-            workers = min(_HOST_THREADS, n * nr * nr // 65536)
-            if workers < 2:
-                return transform(z, j0, j1)
-            cuts = np.linspace(0, n, 2 * workers + 1).astype(np.int64)
-            parts = list(_host_pool().map(lambda ab: transform(z[ab[0]:ab[1]], j0 + ab[0], j0 + ab[1]),
-                                          zip(cuts[:-1], cuts[1:])))
-            return np.concatenate(parts)
-
-        def draw_fb(pats):
-            """np.random.choice(vals, (nfb, nr), p) for every pattern of `pats` [..., npat]: uniforms in order."""
-            u = np.random.random_sample(pats.shape + (nfb, nr))
-            smp = vals[cdf.searchsorted(u, side="right")]
-            relv = ((pats[..., None] >> np.arange(nr - 1, -1, -1)) & 1).astype(bool)     # [..., npat, nr]
-            smp = np.where(relv[..., None, :], smp, -smp)
-            vbit = (1 << np.arange(nr)).astype(np.uint32)
-            nz = ((smp != 0) * vbit).sum(axis=-1).astype(np.uint32)
-            ps = ((smp > 0) * vbit).sum(axis=-1).astype(np.uint32)
-            return nz | (ps << np.uint32(16))
-
-        L = len(live)
-        enum_pats = np.arange(npat, dtype=np.uint32)
-        if rel_mc and not fb_mc:
-            # the legacy generator cannot jump, so every rank walks the whole stream of normals -- but only its own
-            # candidates' are computed (the others are skipped: raw draws and accept tests, ital_np_legacy_normals), and
-            # the decompositions are done for those alone
-            if z_rel is None:
-                z_loc = self._walk_normals(L, jl0, jl1, npat * nr).reshape(-1, npat, nr)
-            else:
-                g0, z = z_rel                                       # drawn ahead for live ranks g0 .. g0 + len(z) - 1
-                z_loc = z[jl0 - g0:jl1 - g0]
-            if chunks > 0 and local is not None and jl1 > jl0:
-                draws = np.zeros(P, dtype=np.int64)
-                draws[live] = npat * (npre_draws[live] + nfb * d_full[live])
-
-                def ranges():
-                    # a SHORT first range: the GPU idles while the host decomposes it (the pick of the step before, the new
-                    # member's covariance column and the SVDs of its candidates: 0.17 s per step at 1M x 512 with four equal
-                    # ranges, 2.8 s of a 101 s round), every later range is decomposed under the lattice sums of the one before
-                    # -- as long as a range is not much longer than the one before (the host decomposes ~1.4 M candidates per
-                    # second on 16 threads, the GPU integrates 1.6 M (7 variables) .. 47 k (16) per second): sizes 1 : 2 : 4 : ...
-                    cuts = _range_cuts(jl0, jl1, chunks)
-                    for a, b_ in zip(cuts[:-1], cuts[1:]):
-                        lo = local[0] if a == jl0 else int(live[a])
-                        hi = local[1] if b_ == jl1 else int(live[b_])
-                        rows = np.zeros((hi - lo, npat), dtype=np.uint32)
-                        rows[live[a:b_] - lo] = draw_rel(int(a), int(b_), z_loc[a - jl0:b_ - jl0])
-                        yield lo, hi, rows, bool(b_ == cuts[-1])
-                return ranges(), None, draws
-            rel_live = np.zeros((L, npat), dtype=np.uint32)
-            if jl1 > jl0:
-                rel_live[jl0:jl1] = draw_rel(jl0, jl1, z_loc)
-        elif fb_mc and not rel_mc:
-            fb_live = draw_fb(np.broadcast_to(enum_pats, (L, npat)))
-        else:
-            rel_live = np.empty((L, npat), dtype=np.uint32)
-            fb_live = np.empty((L, npat, nfb), dtype=np.uint32)
-            for j in range(L):                                       # the two samplers interleave per candidate
-                rel_live[j] = draw_rel(j, j + 1)[0]
-                fb_live[j] = draw_fb(rel_live[j])
-        if rel_mc:
-            rel_arr = np.zeros((P, npat), dtype=np.uint32)
-            rel_arr[live] = rel_live
-        draws = np.zeros(P, dtype=np.int64)
-        if fb_mc:
-            fb_arr = np.zeros((P, npat, nfb), dtype=np.uint32)
-            fb_arr[live] = fb_live
-            calls = ((fb_live & 0xffff) != 0).sum(axis=(1, 2))      # all-zero feedback samples make no call
-            draws[live] = npat * npre_draws[live] + calls * d_full[live]
-        else:
-            draws[live] = npat * (npre_draws[live] + nfb * d_full[live])
-        return rel_arr, fb_arr, draws
+        with torch.cuda.device(self.gp.device):
+            return GenericRound(self, k, candidates).run()

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, sharding
-from ._batch import make_batch_buffers
+from ._batch import FUSED_LAUNCH_MAX, Model, Scored, make_batch_buffers, member_column, select_step
 from ._lib import ITAL_MAX_T, ItalMcmiDesc, check
 from .gp import _pad16, _ptr, _stream
 from .retrieval_base import ActiveRetrievalBase
@@ -93,21 +93,22 @@ class MCMI_min(ActiveRetrievalBase):
                 sharding.all_reduce_sum(buf, gp.group)
         return Xc, Vc, ldc, vec[0], vec[1], vec[2]
 
-    def _round(self, k, cand, b, cov, pos_d, alive, ce, Xc, Vc, ldc, xnc, muc, s2c, st):
+    def _round(self, k, cand, b, cov, scored, block, st):
         """One rank: covariance block, k scoring / arg-min steps and k - 1 covariance columns enqueued by ONE call
         (ital_mcmi_round): at the reference's subsample of 1000 a step is 20 - 90 us of kernels and the launches of a Python
         host are 6 us apart."""
         lib = _lib.lib()
         gp = self.gp
         dev = gp.device
-        nc = len(cand)
+        nc, ldc = len(cand), block.ldv
+        ce, pos_d, alive = scored.scores, scored.cand, scored.alive
         r = b.get("mcmi_round")
         if r is None:
             b["mcmi_round"] = r = _lib.ItalMcmiRoundDesc()
         d = r.step
         r.k = k
         d.n_i, d.pos_offset, d.n_all = nc, 0, nc
-        d.alive, d.mu, d.s2 = _ptr(alive), _ptr(muc), _ptr(s2c)
+        d.alive, d.mu, d.s2 = _ptr(alive), _ptr(block.mu), _ptr(block.s2)
         d.cov, d.ld_cov, d.C, d.ldc = _ptr(cov), ldc, _ptr(b["C"]), ldc
         d.batch = b["batch"]
         d.noise, d.eps, d.ce = float(self.noise), float(self.eps), _ptr(ce)
@@ -118,7 +119,7 @@ class MCMI_min(ActiveRetrievalBase):
             if w is None or w.numel() < want:
                 b["mcmi_work"] = w = torch.empty(want, dtype=torch.float64, device=dev)
             d.work, d.work_doubles = _ptr(w), w.numel()
-        r.Xc, r.xnc, r.ldx, r.Vc, r.ldv, r.m, r.ldw = _ptr(Xc), _ptr(xnc), gp.ldx, _ptr(Vc), ldc, gp.m, gp.cap
+        r.Xc, r.xnc, r.ldx, r.Vc, r.ldv, r.m, r.ldw = _ptr(block.X), _ptr(block.xnorm), gp.ldx, _ptr(block.V), ldc, gp.m, gp.cap
         r.var, r.length_scale = float(self.var), float(self.length_scale)
         r.pos, r.status, r.record, r.ret, r.begin = _ptr(pos_d), _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]), 1
         check(lib.ital_mcmi_round(ctypes.byref(r), st))
@@ -155,6 +156,7 @@ class MCMI_min(ActiveRetrievalBase):
         with torch.cuda.device(dev):
             st = _stream()
             Xc, Vc, ldc, xnc, muc, s2c = self._gather_block(cand)
+            block = Model(muc, s2c, Xc, xnc, nc, gp.ldx, Vc, ldc, gp.m, gp.cap)     # what selection and covariance columns read
             i0, i1 = sharding.row_range(nc, gp.world, gp.rank)
             n_i = i1 - i0
             if max(n_i, 1) * ldc * 8 > self.max_cov_bytes:
@@ -168,9 +170,10 @@ class MCMI_min(ActiveRetrievalBase):
                                     torch.empty(max(n_i, 1), dtype=torch.uint8, device=dev),
                                     torch.empty(max(n_i, 1), dtype=torch.float64, device=dev))
             _, b, cov, pos_d, alive, ce = self._fetch_bufs
+            scored = Scored(ce, pos_d, alive, n_i, i0, None, 0)
             if (self.round_call and not gp.collective and self.profile is None and not self.keep_scores
                     and k <= nc <= (1 << 18)):
-                return self._round(k, cand, b, cov, pos_d, alive, ce, Xc, Vc, ldc, xnc, muc, s2c, st)
+                return self._round(k, cand, b, cov, scored, block, st)
             alive.fill_(1)
             b["ret"][b["kmax"]:].zero_()       # the selection steps OR the status word into this slot
             ev0 = self._mark()
@@ -201,25 +204,9 @@ class MCMI_min(ActiveRetrievalBase):
                 self._mark("mcmi_score", t, nc - (t - 1), ev0)
                 if self.keep_scores:
                     self.last_scores.append(ce.clone())
-                if not gp.collective and n_i <= (1 << 18):
-                    check(lib.ital_select_fused(_ptr(ce), _ptr(pos_d), _ptr(alive), n_i, i0, None, 0, gp.rank, 1, _ptr(muc),
-                                                _ptr(s2c), _ptr(Xc), _ptr(xnc), gp.ldx, _ptr(Vc), ldc, gp.m, gp.cap,
-                                                _ptr(b["C"]), ldc, t - 1, t - 1, b["batch"], _ptr(gp.status), _ptr(b["rec"]),
-                                                _ptr(b["ret"]), st))
-                else:
-                    check(lib.ital_select_local(_ptr(ce), _ptr(pos_d), _ptr(alive), n_i, i0, None, 0, gp.rank, 1, _ptr(muc),
-                                                _ptr(s2c), _ptr(Xc), _ptr(xnc), gp.ldx, _ptr(Vc), ldc, gp.m, gp.cap,
-                                                _ptr(b["C"]), ldc, t - 1, b["kmax"], _ptr(gp.status), _ptr(b["work"]),
-                                                _ptr(b["rec"]), st))
-                    recs = sharding.gather_records(b["rec"], b["rec_all"], gp.group) if gp.collective else b["rec"]
-                    check(lib.ital_select_resolve(_ptr(recs), gp.world, b["rec_len"], gp.rank, 1, t - 1, b["batch"],
-                                                  _ptr(alive), _ptr(b["ret"]), st))
+                select_step(gp, b, scored, block, t - 1, st, argmin=1, fused=not gp.collective and n_i <= FUSED_LAUNCH_MAX)
                 if t < k:
-                    slot = t - 1
-                    check(lib.ital_cross_cov_cols(_ptr(Xc), _ptr(xnc), nc, gp.ldx, _ptr(b["XB"][slot]),
-                                                  _ptr(b["XBn"][slot:]), 1, _ptr(b["VB"][slot]), gp.cap, _ptr(Vc), ldc,
-                                                  gp.m, float(self.var), float(self.length_scale), _ptr(b["C"][slot]),
-                                                  ldc, st))
+                    member_column(self, block, b, t - 1, st)
             host = b["ret"].cpu().tolist()        # block positions + status word; the only synchronisation of the round
         picked = host[:k]
         gp.check_status(host[b["kmax"]])

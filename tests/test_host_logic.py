@@ -279,7 +279,7 @@ def test_host_side_under_address_and_ub_sanitizers():
 
 
 def test_rank_local_walk_of_numpy_stream_partitions_the_reference_draws():
-    """What the Monte-Carlo pattern sampler does on W ranks (ital_amd/ital.py `_walk_normals`): every rank walks numpy's
+    """What the Monte-Carlo pattern sampler does on W ranks (ital_amd/_mc_sampler.py `walk_normals`): every rank walks numpy's
     global generator over ALL candidates' standard normals, computing only those of its own slice.  The slices put together
     are the reference's draws (one multivariate_normal.rvs per candidate in list order, ital.py:297), and every rank's
     generator ends in the reference's state."""
