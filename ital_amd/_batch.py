@@ -110,6 +110,30 @@ def qmc_work(b, want, dev):
     return w
 
 
+def ensure_step_buffers(b, n_loc, sel_doubles, dev):
+    """Buffers of `b` that the fast paths' steps share: alive flags and scores of n_loc candidates (b["alive"], b["mi"]) and,
+    for steps that end with their selection, sel_doubles doubles of block partials with their counter (b["sel_parts"],
+    b["sel_counter"]).  They grow, never shrink; True when one was replaced (what pointed into it is stale)."""
+    grown = False
+    n = max(n_loc, 1)
+    if b.get("alive") is None or b["alive"].numel() < n:
+        b["alive"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        b["mi"] = torch.empty(n, dtype=torch.float64, device=dev)
+        grown = True
+    if sel_doubles and (b.get("sel_parts") is None or b["sel_parts"].numel() < sel_doubles):
+        b["sel_parts"] = torch.empty(sel_doubles, dtype=torch.float64, device=dev)
+        b["sel_counter"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        grown = True
+    return grown
+
+
+def lattice_label(work, t, n_loc):
+    """Profile label of the lattice sums of step t over n_loc candidates: they run in as many slabs as workspace `work`
+    needs to hold the prepared calls of all of them."""
+    slabs = -(-n_loc // max(work.numel() // int(_lib().ital_score_workspace(t, 1)), 1))
+    return "qmc_main" if slabs == 1 else "qmc_slabs%d" % slabs
+
+
 def fill_score_desc(d, gp, b, scored, user):
     """Fields of ital_score_desc that every fast-path step fills alike.  user: (noise, eps, label mode)."""
     s = scored

@@ -11,22 +11,25 @@ kernel enqueued on one stream, with no host round trip inside a round:
 
 Candidates are sharded by rows across ranks; the per-step exchange is ONE fixed-size record per rank.
 
-This module holds the learner, its fast paths (`_select_round`: a whole round as one call below the C ABI; `_select_steps`:
-step by step) and their dispatch.  The round of every other option (`_fetch_generic`) is `_generic_round.GenericRound`, the
-host sampling of the Monte-Carlo switches `_mc_sampler`, the launches all greedy loops share (selection of a step, the new
-member's covariance column, lattice tables, workspace) `_batch`.
+This module holds the learner, the dispatch between its paths and the step-by-step fast path (`_select_steps`).  A whole
+round as one call below the C ABI (`_select_round`) is `_fast_round.FastRound`, which also keeps that path's state between
+rounds (`_fast_round.RoundBuffers`: the candidate list on the device, the prepared next round); the round of every other
+option (`_fetch_generic`) is `_generic_round.GenericRound`, the host sampling of the Monte-Carlo switches `_mc_sampler`,
+the launches and buffers all greedy loops share (selection of a step, the new member's covariance column, lattice tables,
+workspace, alive flags and selection partials) `_batch`.
 """
 import ctypes
 import os
-import time
 
 import numpy as np
 import torch
 
 from . import _lib, _mc_sampler, mvn_stream, sharding
 from ._lib import ITAL_GENERIC_MAX_CALLS, ITAL_GENERIC_MAX_DIM, ITAL_GENERIC_MAX_REL, ITAL_MAX_T, ItalScoreDesc, check
-from ._batch import (FUSED_LAUNCH_MAX as _FUSED_LAUNCH_MAX, LABEL_MODES as _LABEL_MODES, Scored, fill_score_desc,
-                     fill_score_select, gp_model, lattice_tables, make_batch_buffers, member_column, qmc_work, select_step)
+from ._batch import (FUSED_LAUNCH_MAX as _FUSED_LAUNCH_MAX, LABEL_MODES as _LABEL_MODES, Scored, ensure_step_buffers,
+                     fill_score_desc, fill_score_select, gp_model, lattice_label, lattice_tables, make_batch_buffers,
+                     member_column, qmc_work, select_step)
+from ._fast_round import FastRound
 from ._generic_round import GenericRound
 from ._mc_sampler import range_cuts as _range_cuts   # noqa: F401 -- tests/test_host_logic.py imports it from here
 from .gp import _ptr, _stream
@@ -74,7 +77,10 @@ class ITAL(ActiveRetrievalBase):
         self._fetch_bufs = None
         self.profile_steps = None      # round path: greedy steps whose lattice sums are bracketed by events (None: all)
         self.round_call = True        # up to ITAL_ROUND_MAX_CAND candidates per rank: a whole round through ital_fetch_round (False: step by step from Python)
-        self._dev_list = None         # the candidate list the device holds: (buffers, UnseenList and its version, picks flagged dead)
+        self._round_bufs = None       # _fast_round.RoundBuffers of _fetch_bufs: what only the one-call round keeps between rounds
+        self.last_round = None        # (begin, descriptor slot) of the last one-call round: how its candidate list reached the device (diagnostics / tests)
+        self._transport = None        # (process group, _round_transport() for it)
+        self._pinned = {}             # page-locked landing buffers of _download on several ranks
         self.select_in_scorer = True  # False: the selection of a greedy step always runs as a launch of its own (cross-check in tests)
         self.mc_walk = [0, 0, 0.0]   # Monte-Carlo pattern sampling: standard normals computed / skipped, host seconds
         self.host_clock = None       # dict(gap_s=0.0, gaps=0, enqueue_s=0.0, t_download=None): host time of the round path (bench.py)
@@ -160,8 +166,13 @@ class ITAL(ActiveRetrievalBase):
         b = make_batch_buffers(gp.device, kmax, gp.ldx, gp.cap, gp.ldv, gp.world)
         b["gp"] = gp              # fit() on an existing learner builds a new GP (other row count / dimension): new buffers
         self._fetch_bufs = b
-        self._dev_list = None
+        self._round_bufs = None
         return b
+
+    @property
+    def _dev_list(self):
+        """The candidate list the device holds (_fast_round.DeviceList); None unless the next round may follow it."""
+        return None if self._round_bufs is None else self._round_bufs.device_list
 
     def _candidate_list(self, candidates=None):
         """Candidate list in the reference's order (ital.py:98, :111-117) as an int64 array."""
@@ -234,9 +245,7 @@ class ITAL(ActiveRetrievalBase):
             torch.zeros(1, dtype=torch.int32, device=dev)
         gpos_d = torch.from_numpy(gpos).to(dev) if gpos is not None else None
         if b is not None:
-            if b.get("alive") is None or b["alive"].numel() < max(n_loc, 1):
-                b["alive"] = torch.empty(max(n_loc, 1), dtype=torch.uint8, device=dev)
-                b["mi"] = torch.empty(max(n_loc, 1), dtype=torch.float64, device=dev)
+            ensure_step_buffers(b, n_loc, 0, dev)
             alive = b["alive"]
             alive.fill_(1)
         else:
@@ -262,15 +271,14 @@ class ITAL(ActiveRetrievalBase):
 
     def _select(self, k, candidates):
         """Greedy construction of a batch of k out of `candidates` (k <= len(candidates))."""
-        gp = self.gp
-        self._last_batch = None        # published only after the round's final successful download (update() pairs its
-        if self._needs_generic():      # sample ids with rows of the batch buffers)
-            self._dev_list = None
-            return self._fetch_generic(k, candidates)
-        if self.round_call and self.select_in_scorer and self._round_possible(k, candidates):
+        # (published only after the round's final successful download: update() pairs its sample ids with rows of the batch buffers)
+        self._last_batch = None
+        generic = self._needs_generic()
+        if not generic and self.round_call and self.select_in_scorer and self._round_possible(k, candidates):
             return self._select_round(k, candidates)
-        self._dev_list = None
-        return self._select_steps(k, candidates)
+        if self._round_bufs is not None:
+            self._round_bufs.invalidate()      # the other paths leave the device's list behind
+        return self._fetch_generic(k, candidates) if generic else self._select_steps(k, candidates)
 
     def _user(self):
         """(noise, eps, label mode) of ital_score_desc."""
@@ -278,7 +286,7 @@ class ITAL(ActiveRetrievalBase):
 
     def _step_desc(self, b, scored, t, k, n_alive, tail, fused):
         """ital_score_desc of greedy step t of the step-by-step path (tail: the scoring launch ends with the selection)."""
-        lib, gp = _lib.lib(), self.gp
+        gp = self.gp
         n_loc = scored.n
         desc = ItalScoreDesc()
         desc.t = t
@@ -298,17 +306,12 @@ class ITAL(ActiveRetrievalBase):
                 k0, k1 = self._event(), self._event()
                 desc.ev_start, desc.ev_stop = k0.cuda_event, k1.cuda_event
                 # several slabs: the pair spans first .. last lattice sum incl. the launches between them
-                slabs = -(-n_loc // max(work.numel() // int(lib.ital_score_workspace(t, 1)), 1))
-                self.profile.append(("qmc_main" if slabs == 1 else "qmc_slabs%d" % slabs, t,
-                                     n_alive if not gp.collective else n_loc, k0, k1))
+                self.profile.append((lattice_label(work, t, n_loc), t, n_alive if not gp.collective else n_loc, k0, k1))
         if tail:
             # the scoring launch ends with the selection itself (the block that finishes last selects): one rank --
             # arg-max, record and batch bookkeeping, no selection launch at all; several ranks -- arg-max and record
             # (what ital_select_local does in a single-workgroup launch of its own), exchange and resolve follow
-            parts = b.get("sel_parts")
-            if parts is None or parts.numel() < self._sel_parts_doubles(k, n_loc):
-                b["sel_parts"] = torch.empty(self._sel_parts_doubles(k, n_loc), dtype=torch.float64, device=gp.device)
-                b["sel_counter"] = torch.zeros(1, dtype=torch.int32, device=gp.device)
+            ensure_step_buffers(b, n_loc, self._sel_parts_doubles(k, n_loc), gp.device)
             fill_score_select(desc, gp, b, gp.m, b["ret"] if fused else None)
         return desc
 
@@ -347,7 +350,7 @@ class ITAL(ActiveRetrievalBase):
                     if t == 1:
                         self._mark("cross_cov", t, gp.m, ev0)
                 # the reference's serial loop has now consumed this many uniforms of mvndst's stream
-                stream.advance(n_alive * (2 << t) * mvn_stream.draws_per_call(t))
+                stream.advance(mvn_stream.step_draws(t, n_alive))
                 n_alive -= 1
             host = self._download(b["ret"], "the picks of the round", self._step_estimate_s(k, n_loc)).tolist()     # the only synchronisation of the round: the picks and the status word
             ret, status = host[:k], host[b["kmax"]]   # status: OR over the greedy steps and over all ranks (same everywhere)
@@ -398,15 +401,12 @@ class ITAL(ActiveRetrievalBase):
         gp = self.gp
         if not gp.collective:
             return tensor.cpu()
-        kind = getattr(self, "_transport", None)
-        kind = kind[1] if kind else None
+        kind = self._transport[1] if self._transport else None
         comm = kind[1] if kind and kind[0] == "nccl" else None
         if comm is None:
             e = sharding._RAW_COMMS.get((id(gp.group), str(gp.device)))      # the step path uses the raw communicator as well
             comm = e[1] if e else None
         name = {"nccl": "raw_nccl", "host": "host"}[kind[0]] if kind else ("raw_nccl (per step)" if comm else "torch_dist")
-        if getattr(self, "_pinned", None) is None:
-            self._pinned = {}
         return sharding.await_download(tensor, what, gp.group, gp.device, comm, gp.rank, gp.world, name, pinned=self._pinned,
                                        step_estimate_s=step_estimate_s)
 
@@ -416,7 +416,7 @@ class ITAL(ActiveRetrievalBase):
         a callback (backends that move host memory: the gloo rehearsals and tests), or None (the round is enqueued step by
         step with torch.distributed's all-gather between the launches)."""
         gp = self.gp
-        cached = getattr(self, "_transport", None)
+        cached = self._transport
         if cached is not None and cached[0] is gp.group:
             return cached[1]
         kind = None
@@ -435,199 +435,12 @@ class ITAL(ActiveRetrievalBase):
             self._transport = (gp.group, kind)
         return kind
 
-    def _host_exchange(self, b):
-        """The record exchange as a callback of ital_fetch_round (transport "host"): torch.distributed's all-gather of this
-        rank's record buffer, issued from inside the C call at the place the RCCL transport issues ncclAllGather."""
-        cb = b.get("exchange_cb")
-        if cb is None:
-            group = self.gp.group
-
-            def exchange(ctx, record, records_all, rec_len, stream):
-                try:
-                    sharding.gather_records(b["rec"], b["rec_all"], group)
-                    return 0
-                except Exception as e:      # noqa: BLE001 -- must not unwind through the C frames
-                    b["exchange_exc"] = e   # re-raised by the caller of ital_fetch_round (an ExchangeError: deadline / lost peer)
-                    return -5
-            b["exchange_cb"] = cb = _lib.EXCHANGE_FN(exchange)
-        return cb
-
-    def _round_signature(self, b, k):
-        gp = self.gp
-        w = b.get("qmc_work")
-        return (id(b), k, gp.cap, gp.ldv, gp.V.data_ptr(), gp.mu.data_ptr(), 0 if w is None else w.data_ptr(),
-                float(self.noise), float(self.eps),
-                float(self.var), float(self.length_scale), self.label_estimation, self.qmc_work_bytes,
-                self.profile is not None, repr(self.profile_steps))
-
-    def _round_prepare(self, slot, b, k, n, m, begin, cur, state_before, *, n_prev=0, n_loc=None, pos_offset=0):
-        """Fills round descriptor `slot` (one of two) for a round of k steps over n candidates with m labelled samples, the
-        candidate list in device buffer `cur` (begin = 2: compacted out of the other buffer, which holds n_prev entries).
-        Several ranks: n_loc of the n candidates are this rank's, the first of them at list position pos_offset.
-        Nothing here depends on the picks of the round before: the descriptor of the NEXT round is prepared while the GPU
-        works on the current one, off the critical path of the retrieval loop."""
-        lib = _lib.lib()
-        gp = self.gp
-        dev = gp.device
-        lists = b["cand_lists"]
-        r = b["round_descs"][slot]
-        d = r.step
-        r.k, r.n_rows, r.var, r.length_scale = k, gp.n, float(self.var), float(self.length_scale)
-        r.begin, r.cand_prev, r.n_prev = begin, (_ptr(lists[cur ^ 1]) if begin == 2 else None), (n_prev if begin == 2 else 0)
-        n_loc = n if n_loc is None else n_loc
-        fill_score_desc(d, gp, b, Scored(b["mi"], lists[cur], b["alive"], n_loc, pos_offset, None, gp.row0), self._user())
-        r.world, r.records_all, r.nccl_comm, r.exchange = 0, None, None, _lib.EXCHANGE_FN(0)
-        if gp.collective:
-            kind, comm = self._round_transport()
-            r.world, r.records_all = gp.world, _ptr(b["rec_all"])
-            if kind == "nccl":
-                r.nccl_comm = comm
-            else:
-                r.exchange = self._host_exchange(b)
-        fill_score_select(d, gp, b, m, b["ret"])
-        r.mi_keep = None
-        events = []
-        if k >= 3:
-            work = self._qmc_workspace(b, k, n_loc)
-            d.work, d.work_doubles = _ptr(work), work.numel()
-        for t in range(1, k + 1):
-            r.ev_start[t] = r.ev_stop[t] = None
-            if t >= 3:
-                r.jump[t], r.jumppat[t], r.vk[t] = [_ptr(x) for x in lattice_tables(b, t, dev)]
-                if self.profile is not None and (self.profile_steps is None or t in self.profile_steps):
-                    k0, k1 = self._event(), self._event()
-                    r.ev_start[t], r.ev_stop[t] = k0.cuda_event, k1.cuda_event
-                    slabs = -(-n_loc // max(work.numel() // int(lib.ital_score_workspace(t, 1)), 1))
-                    # (candidates the bracketed launches score: the whole list on one rank; this rank's share otherwise --
-                    # which rank the earlier picks of the round come from is not known when the descriptor is built)
-                    events.append(("qmc_main" if slabs == 1 else "qmc_slabs%d" % slabs, t,
-                                   n - (t - 1) if not gp.collective else n_loc, k0, k1))
-        # the reference's serial loop consumes n_alive * 2 * 2^t calls of mvndst's stream at step t: states before every step
-        st6 = (ctypes.c_int * 6)(*state_before)
-        check(lib.ital_mvn_round_seeds(st6, n, k, ctypes.byref(r.seeds)))
-        draws = sum((n - (t - 1)) * (2 << t) * mvn_stream.draws_per_call(t) for t in range(3, k + 1))
-        return dict(slot=slot, k=k, n=n, n_loc=n_loc, m=m, begin=begin, cur=cur, state_before=tuple(state_before),
-                    state_after=tuple(int(v) for v in st6), draws=draws, events=events, sig=self._round_signature(b, k))
-
     def _select_round(self, k, candidates):
-        """_select as ONE call below the C ABI (ital_fetch_round): candidate-list upkeep, k scoring steps that end with
-        their selection (several ranks: with the rank's record, then the exchange issued from C and the resolve launch),
-        k - 1 covariance columns -- enqueued from C (a Python host needs 10 - 17 us per launch, the first greedy steps are
-        shorter than that).  Several ranks work on their own share of the list (list positions lo .. hi).  The candidate list stays on the device between rounds: when
-        the list is the previous one minus the previous batch (the retrieval loop: fetch, label the batch, fetch), it is
-        compacted there by its alive flags instead of being rebuilt and uploaded; and the descriptor of such a next round
-        is filled in while the GPU still works on the current one."""
-        t_enter = time.perf_counter()
-        lib = _lib.lib()
-        gp = self.gp
-        dev = gp.device
-        n = len(candidates)
-        listed = isinstance(candidates, UnseenList)      # (several ranks: always, see _round_possible)
-        if gp.collective:
-            # this rank's share of the ascending list: one run of it, list positions lo .. hi
-            lo, hi = candidates.count_below(gp.row0), candidates.count_below(gp.row1)
-        else:
-            lo, hi = 0, n
-        n_loc = hi - lo
-        with torch.cuda.device(dev):
-            b = self._buffers(k)
-            st = _stream()
-            # ---- candidate list: two device buffers (the compaction reads one, writes the other)
-            lists = b.get("cand_lists")
-            if lists is None or lists[0].numel() < n_loc or b.get("alive") is None or b["alive"].numel() < n_loc \
-                    or b["sel_parts"].numel() < self._sel_parts_doubles(k, n_loc):
-                b["cand_lists"] = lists = [torch.empty(max(n_loc, 1), dtype=torch.int32, device=dev) for _ in range(2)]
-                b["cand_cur"] = 0
-                b["alive"] = torch.empty(n_loc, dtype=torch.uint8, device=dev)
-                b["mi"] = torch.empty(n_loc, dtype=torch.float64, device=dev)
-                b["sel_parts"] = torch.empty(self._sel_parts_doubles(k, n_loc), dtype=torch.float64, device=dev)
-                b["sel_counter"] = torch.zeros(1, dtype=torch.int32, device=dev)
-                b["round_descs"] = [_lib.ItalRoundDesc(), _lib.ItalRoundDesc()]
-                b["round_next"] = None
-                self._dev_list = None
-            dl = self._dev_list
-            stream = mvn_stream.GLOBAL
-            # the device holds the list as of version v with the picks of that round flagged dead: it follows the host's
-            # when the host's list is that version minus exactly those picks
-            follows = (listed and dl is not None and dl["b"] is b and dl["unseen"] is candidates
-                       and dl["version"] == candidates.version - 1 and tuple(sorted(dl["picks"])) == candidates.last_removed)
-            self._dev_list = None                              # re-published after the round's successful download
-            p = b["round_next"]
-            if (p is not None and follows and not self.keep_scores and p["k"] == k and p["n"] == n and p["m"] == gp.m
-                    and p["state_before"] == tuple(stream.state) and p["sig"] == self._round_signature(b, k)):
-                b["cand_cur"] = p["cur"]                       # the round the previous one prepared for
-                if gp.collective:
-                    # prepared before the picks were known: how many of them lay in this rank's rows and before them
-                    d = b["round_descs"][p["slot"]].step
-                    d.n_cand, d.pos_offset = n_loc, lo
-                    p["n_loc"] = n_loc
-                    for i, ev in enumerate(p["events"]):
-                        p["events"][i] = ev[:2] + (n_loc,) + ev[3:]
-            else:
-                if p is not None:                              # prepared for a round that did not come: its events go back
-                    for ev in p["events"]:
-                        self.event_pool += [ev[3], ev[4]]
-                n_prev = 0
-                if follows:
-                    begin, n_prev = 2, dl["n_loc"]             # the device holds the parent list with exactly those picks flagged
-                    b["cand_cur"] ^= 1
-                else:
-                    begin = 1
-                    share = candidates.in_rows(gp.row0, gp.row1) if listed else np.asarray(candidates, dtype=np.int64)
-                    lists[b["cand_cur"]][:n_loc].copy_(torch.from_numpy((share - gp.row0).astype(np.int32)))
-                p = self._round_prepare(0, b, k, n, gp.m, begin, b["cand_cur"], stream.state, n_prev=n_prev, n_loc=n_loc,
-                                        pos_offset=lo)
-            b["round_next"] = None
-            self.last_round = (p["begin"], p["slot"])          # diagnostics / tests: how the candidate list reached the device
-            r = b["round_descs"][p["slot"]]
-            keep = None
-            if self.keep_scores:
-                keep = torch.zeros((k, n_loc), dtype=torch.float64, device=dev)
-                r.mi_keep = _ptr(keep)
-            saved_stream = (stream.state, stream.draws)
-            hc = self.host_clock
-            if hc is not None:
-                # host time on the critical path of the retrieval loop: from the download of the previous round's picks (the
-                # caller's feedback, update(), this prologue) to the call that enqueues the next round
-                t_call = time.perf_counter()
-                if hc.get("t_download") is not None:
-                    hc["gap_s"] += t_call - hc["t_download"]
-                    hc["gaps"] += 1
-                    hc["prologue_s"] = hc.get("prologue_s", 0.0) + (t_call - t_enter)
-            rc = lib.ital_fetch_round(ctypes.byref(r), st)
-            if rc and b.get("exchange_exc") is not None:      # the host transport's callback failed: its own error, not the C one
-                exc, b["exchange_exc"] = b["exchange_exc"], None
-                raise exc
-            check(rc)
-            stream.state, stream.draws = p["state_after"], stream.draws + p["draws"]
-            if self.profile is not None:
-                self.profile += p["events"]
-            # ---- while the GPU works: the descriptor of the round that follows in the retrieval loop (this batch labelled,
-            # then the next fetch of k): nothing in it depends on which samples this round picks
-            if n - k >= k and gp.m + k <= gp.cap and not self.keep_scores:
-                # (several ranks: this rank's share of that list is known only with the picks -- patched in when the round comes)
-                b["round_next"] = self._round_prepare(p["slot"] ^ 1, b, k, n - k, gp.m + k, 2, b["cand_cur"] ^ 1, stream.state,
-                                                      n_prev=n_loc, n_loc=n_loc if gp.collective else n - k, pos_offset=lo)
-            if hc is not None:
-                hc["enqueue_s"] += time.perf_counter() - t_call     # the call itself + the next round's descriptor (GPU busy)
-            host = self._download(b["ret"], "the picks of the round", self._step_estimate_s(k, n_loc)).tolist()     # the only synchronisation of the round: the picks and the status word
-            if hc is not None:
-                hc["t_download"] = time.perf_counter()
-            ret, status = host[:k], host[b["kmax"]]
-            self.last_scores = [keep[t, :n_loc] for t in range(k)] if keep is not None else []
-            if status & 8:
-                raise RuntimeError("ital_amd: the candidate list kept on the device lost track of the host's (internal error)")
-            if status & 6:
-                # see _select: duplicates inside the batch / a simulated update that does not pin the labels
-                gp.status.bitwise_and_(~6)
-                stream.state, stream.draws = saved_stream
-                return self._fetch_generic(k, candidates.array() if listed else candidates)
-        if status:
-            gp.check_status(status)
-        self._last_batch = (b, list(ret))
-        if listed:
-            self._dev_list = dict(b=b, unseen=candidates, version=candidates.version, picks=[int(i) for i in ret], n_loc=n_loc)
-        return [int(i) for i in ret]
+        """_select as ONE call below the C ABI (ital_fetch_round); the candidate list stays on the device between rounds.
+        The round itself is _fast_round.FastRound."""
+        round_ = FastRound(self, k, candidates)            # (the host clock of the round's prologue starts here)
+        with torch.cuda.device(self.gp.device):
+            return round_.run()
 
     # ------------------------------------------------------------------ general scorer (noisy users, estimation subset)
     def _fetch_generic(self, k, candidates):

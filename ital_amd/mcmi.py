@@ -12,6 +12,7 @@ the arg-min greedily (mcmi.py:69-79).  On the device:
 With several ranks the scored candidates (rows i of the pairwise objective) are split across ranks, the block they
 are scored against is replicated.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -22,6 +23,13 @@ from ._batch import FUSED_LAUNCH_MAX, Model, Scored, make_batch_buffers, member_
 from ._lib import ITAL_MAX_T, ItalMcmiDesc, check
 from .gp import _pad16, _ptr, _stream
 from .retrieval_base import ActiveRetrievalBase
+
+
+# the replicated candidate block kept between fetches of one shape (key): features, whitened columns, (norms, means, variances)
+BlockBufs = collections.namedtuple("BlockBufs", "key X V vec")
+# what a fetch of one shape (key) keeps: batch buffers, the own candidates' covariance block, their block positions, alive
+# flags and scores
+FetchBufs = collections.namedtuple("FetchBufs", "key b cov pos alive ce")
 
 
 class MCMI_min(ActiveRetrievalBase):
@@ -77,10 +85,10 @@ class MCMI_min(ActiveRetrievalBase):
         # block buffers are kept between fetches of the same shape (a round at the reference's subsample of 1000 is 0.2 ms of
         # kernels: allocations and fills are most of its host time); the padding stays zero, the rest is overwritten
         key = (nc, gp.ldx, gp.cap)
-        if self._block_bufs is None or self._block_bufs[0] != key:
-            self._block_bufs = (key, torch.zeros((nc, gp.ldx), dtype=torch.float64, device=dev),
-                                torch.zeros((gp.cap, ldc), dtype=torch.float64, device=dev),
-                                torch.zeros((3, nc), dtype=torch.float64, device=dev))
+        if self._block_bufs is None or self._block_bufs.key != key:
+            self._block_bufs = BlockBufs(key, torch.zeros((nc, gp.ldx), dtype=torch.float64, device=dev),
+                                         torch.zeros((gp.cap, ldc), dtype=torch.float64, device=dev),
+                                         torch.zeros((3, nc), dtype=torch.float64, device=dev))
         _, Xc, Vc, vec = self._block_bufs
         # one launch: rows, whitened columns, norms, means and variances of the listed samples (zeros for samples of other
         # ranks); the list travels as one small upload
@@ -93,40 +101,95 @@ class MCMI_min(ActiveRetrievalBase):
                 sharding.all_reduce_sum(buf, gp.group)
         return Xc, Vc, ldc, vec[0], vec[1], vec[2]
 
-    def _round(self, k, cand, b, cov, scored, block, st):
+    def _buffers(self, k, n_i, i0, ldc):
+        """Buffers of a fetch of k picks scoring the n_i candidates from block position i0 on (block columns: ldc)."""
+        gp = self.gp
+        dev = gp.device
+        key = (k, gp.ldx, gp.cap, ldc, n_i, i0)
+        if self._fetch_bufs is None or self._fetch_bufs.key != key:
+            self._fetch_bufs = FetchBufs(key, make_batch_buffers(dev, k, gp.ldx, gp.cap, ldc, gp.world),
+                                         torch.empty((max(n_i, 1), ldc), dtype=torch.float64, device=dev),
+                                         torch.arange(i0, max(i0 + n_i, i0 + 1), dtype=torch.int32, device=dev),
+                                         torch.empty(max(n_i, 1), dtype=torch.uint8, device=dev),
+                                         torch.empty(max(n_i, 1), dtype=torch.float64, device=dev))
+        return self._fetch_bufs
+
+    def _fill_desc(self, d, fb, scored, block, nc):
+        """Fields of ital_mcmi_desc every step of a fetch shares: the scored candidates, the block of nc they are scored
+        against, the covariance block, the members' columns and the batch state."""
+        d.n_i, d.pos_offset, d.n_all = scored.n, scored.pos_offset, nc
+        d.alive, d.mu, d.s2 = _ptr(scored.alive), _ptr(block.mu), _ptr(block.s2)
+        d.cov, d.ld_cov, d.C, d.ldc = _ptr(fb.cov), block.ldv, _ptr(fb.b["C"]), block.ldv
+        d.batch = fb.b["batch"]
+        d.noise, d.eps, d.ce = float(self.noise), float(self.eps), _ptr(scored.scores)
+
+    def _workspace(self, d, b, t, n):
+        """Workspace of the steps t >= 5 (preparation kernel + one workgroup per (candidate, group of label patterns)) over
+        n candidates into descriptor d; when it has to grow it is sized for the largest batch."""
+        lib = _lib.lib()
+        w = b.get("mcmi_work")
+        if w is None or w.numel() < int(lib.ital_mcmi_workspace(t, n)):
+            b["mcmi_work"] = w = torch.empty(int(lib.ital_mcmi_workspace(ITAL_MAX_T, n)), dtype=torch.float64,
+                                             device=self.gp.device)
+        d.work, d.work_doubles = _ptr(w), w.numel()
+
+    def _round(self, k, fb, scored, block, st):
         """One rank: covariance block, k scoring / arg-min steps and k - 1 covariance columns enqueued by ONE call
         (ital_mcmi_round): at the reference's subsample of 1000 a step is 20 - 90 us of kernels and the launches of a Python
         host are 6 us apart."""
-        lib = _lib.lib()
-        gp = self.gp
-        dev = gp.device
-        nc, ldc = len(cand), block.ldv
-        ce, pos_d, alive = scored.scores, scored.cand, scored.alive
+        gp, b = self.gp, fb.b
         r = b.get("mcmi_round")
         if r is None:
             b["mcmi_round"] = r = _lib.ItalMcmiRoundDesc()
         d = r.step
         r.k = k
-        d.n_i, d.pos_offset, d.n_all = nc, 0, nc
-        d.alive, d.mu, d.s2 = _ptr(alive), _ptr(block.mu), _ptr(block.s2)
-        d.cov, d.ld_cov, d.C, d.ldc = _ptr(cov), ldc, _ptr(b["C"]), ldc
-        d.batch = b["batch"]
-        d.noise, d.eps, d.ce = float(self.noise), float(self.eps), _ptr(ce)
+        self._fill_desc(d, fb, scored, block, block.n)
         d.work, d.work_doubles = None, 0
         if k >= 5:
-            want = int(lib.ital_mcmi_workspace(ITAL_MAX_T, nc))
-            w = b.get("mcmi_work")
-            if w is None or w.numel() < want:
-                b["mcmi_work"] = w = torch.empty(want, dtype=torch.float64, device=dev)
-            d.work, d.work_doubles = _ptr(w), w.numel()
-        r.Xc, r.xnc, r.ldx, r.Vc, r.ldv, r.m, r.ldw = _ptr(block.X), _ptr(block.xnorm), gp.ldx, _ptr(block.V), ldc, gp.m, gp.cap
+            self._workspace(d, b, ITAL_MAX_T, block.n)
+        r.Xc, r.xnc, r.ldx, r.Vc, r.ldv, r.m, r.ldw = (_ptr(block.X), _ptr(block.xnorm), gp.ldx, _ptr(block.V), block.ldv, gp.m,
+                                                       gp.cap)
         r.var, r.length_scale = float(self.var), float(self.length_scale)
-        r.pos, r.status, r.record, r.ret, r.begin = _ptr(pos_d), _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]), 1
-        check(lib.ital_mcmi_round(ctypes.byref(r), st))
+        r.pos, r.status, r.record, r.ret, r.begin = _ptr(scored.cand), _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]), 1
+        check(_lib.lib().ital_mcmi_round(ctypes.byref(r), st))
         self.last_scores = []
-        host = b["ret"].cpu().tolist()            # block positions + status word; the only synchronisation of the round
+
+    def _steps(self, k, fb, scored, block, st):
+        """The same round step by step from here (several ranks, profiles, kept scores): covariance block, then per step
+        the scores, the arg-min selection and the picked member's covariance column."""
+        lib = _lib.lib()
+        gp, b = self.gp, fb.b
+        nc, ldc, n_i, i0 = block.n, block.ldv, scored.n, scored.pos_offset
+        scored.alive.fill_(1)
+        b["ret"][b["kmax"]:].zero_()       # the selection steps OR the status word into this slot
+        ev0 = self._mark()
+        if n_i:
+            check(lib.ital_cov_block(_ptr(block.X[i0:]), _ptr(block.xnorm[i0:]), n_i, _ptr(block.X), _ptr(block.xnorm), nc,
+                                     gp.ldx, block.V.data_ptr() + 8 * i0, ldc, _ptr(block.V), ldc, gp.m, float(self.var),
+                                     float(self.length_scale), _ptr(fb.cov), ldc, st))
+        self._mark("cov_block", 0, nc, ev0)
+        self.last_scores = []
+        for t in range(1, k + 1):
+            desc = ItalMcmiDesc()
+            desc.t = t
+            self._fill_desc(desc, fb, scored, block, nc)
+            if t >= 5 and n_i:
+                self._workspace(desc, b, t, n_i)
+            ev0 = self._mark()
+            check(lib.ital_mcmi_score_step(ctypes.byref(desc), st))
+            self._mark("mcmi_score", t, nc - (t - 1), ev0)
+            if self.keep_scores:
+                self.last_scores.append(scored.scores.clone())
+            select_step(gp, b, scored, block, t - 1, st, argmin=1, fused=not gp.collective and n_i <= FUSED_LAUNCH_MAX)
+            if t < k:
+                member_column(self, block, b, t - 1, st)
+
+    def _finish(self, k, cand, b):
+        """Download of the picks (block positions) and the status word, the only synchronisation of the round; publishes
+        the batch for update() and the candidates the fetch leaves behind."""
+        host = b["ret"].cpu().tolist()
         picked = host[:k]
-        gp.check_status(host[b["kmax"]])
+        self.gp.check_status(host[b["kmax"]])
         ret = [int(cand[p]) for p in picked]
         self._last_batch = (b, ret)
         self._candidates = (cand, picked)                    # as `del self.candidates[min_ind]` per pick (mcmi.py:79)
@@ -148,12 +211,10 @@ class MCMI_min(ActiveRetrievalBase):
             return []
         if k > ITAL_MAX_T:
             raise NotImplementedError("batches larger than %d are not enumerated on the device" % ITAL_MAX_T)
-        lib = _lib.lib()
-        dev = gp.device
         self._last_batch = None      # published after the round's successful download only
         cand = np.asarray(cand, dtype=np.int64)
         nc = len(cand)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(gp.device):
             st = _stream()
             Xc, Vc, ldc, xnc, muc, s2c = self._gather_block(cand)
             block = Model(muc, s2c, Xc, xnc, nc, gp.ldx, Vc, ldc, gp.m, gp.cap)     # what selection and covariance columns read
@@ -162,55 +223,11 @@ class MCMI_min(ActiveRetrievalBase):
             if max(n_i, 1) * ldc * 8 > self.max_cov_bytes:
                 raise MemoryError("MCMI_min: %d x %d covariance block; pass subsample= (reference configs use 1000)"
                                   % (n_i, nc))
-            key = (k, gp.ldx, gp.cap, ldc, n_i, i0)
-            if self._fetch_bufs is None or self._fetch_bufs[0] != key:
-                self._fetch_bufs = (key, make_batch_buffers(dev, k, gp.ldx, gp.cap, ldc, gp.world),
-                                    torch.empty((max(n_i, 1), ldc), dtype=torch.float64, device=dev),
-                                    torch.arange(i0, max(i1, i0 + 1), dtype=torch.int32, device=dev),
-                                    torch.empty(max(n_i, 1), dtype=torch.uint8, device=dev),
-                                    torch.empty(max(n_i, 1), dtype=torch.float64, device=dev))
-            _, b, cov, pos_d, alive, ce = self._fetch_bufs
-            scored = Scored(ce, pos_d, alive, n_i, i0, None, 0)
+            fb = self._buffers(k, n_i, i0, ldc)
+            scored = Scored(fb.ce, fb.pos, fb.alive, n_i, i0, None, 0)
             if (self.round_call and not gp.collective and self.profile is None and not self.keep_scores
                     and k <= nc <= (1 << 18)):
-                return self._round(k, cand, b, cov, scored, block, st)
-            alive.fill_(1)
-            b["ret"][b["kmax"]:].zero_()       # the selection steps OR the status word into this slot
-            ev0 = self._mark()
-            if n_i:
-                check(lib.ital_cov_block(_ptr(Xc[i0:]), _ptr(xnc[i0:]), n_i, _ptr(Xc), _ptr(xnc), nc, gp.ldx,
-                                         Vc.data_ptr() + 8 * i0, ldc, _ptr(Vc), ldc, gp.m, float(self.var),
-                                         float(self.length_scale), _ptr(cov), ldc, st))
-            self._mark("cov_block", 0, nc, ev0)
-            self.last_scores = []
-            for t in range(1, k + 1):
-                desc = ItalMcmiDesc()
-                desc.t, desc.n_i, desc.pos_offset, desc.n_all = t, n_i, i0, nc
-                desc.alive, desc.mu, desc.s2 = _ptr(alive), _ptr(muc), _ptr(s2c)
-                desc.cov, desc.ld_cov, desc.C, desc.ldc = _ptr(cov), ldc, _ptr(b["C"]), ldc
-                desc.batch = b["batch"]
-                desc.noise, desc.eps = float(self.noise), float(self.eps)
-                desc.ce = _ptr(ce)
-                if t >= 5 and n_i:
-                    # batches of 5 .. 8: preparation kernel + one workgroup per (candidate, group of label patterns)
-                    want = int(lib.ital_mcmi_workspace(t, n_i))
-                    w = b.get("mcmi_work")
-                    if w is None or w.numel() < want:
-                        b["mcmi_work"] = w = torch.empty(int(lib.ital_mcmi_workspace(ITAL_MAX_T, n_i)), dtype=torch.float64,
-                                                         device=dev)
-                    desc.work, desc.work_doubles = _ptr(w), w.numel()
-                ev0 = self._mark()
-                check(lib.ital_mcmi_score_step(ctypes.byref(desc), st))
-                self._mark("mcmi_score", t, nc - (t - 1), ev0)
-                if self.keep_scores:
-                    self.last_scores.append(ce.clone())
-                select_step(gp, b, scored, block, t - 1, st, argmin=1, fused=not gp.collective and n_i <= FUSED_LAUNCH_MAX)
-                if t < k:
-                    member_column(self, block, b, t - 1, st)
-            host = b["ret"].cpu().tolist()        # block positions + status word; the only synchronisation of the round
-        picked = host[:k]
-        gp.check_status(host[b["kmax"]])
-        ret = [int(cand[p]) for p in picked]
-        self._last_batch = (b, ret)
-        self._candidates = (cand, picked)                    # as `del self.candidates[min_ind]` per pick (mcmi.py:79)
-        return ret
+                self._round(k, fb, scored, block, st)
+            else:
+                self._steps(k, fb, scored, block, st)
+            return self._finish(k, cand, fb.b)

@@ -28,6 +28,12 @@ def draws_per_call(n):
     return 0 if n <= 2 else 8 * (2 * (n - 1) - 1)
 
 
+def step_draws(t, n_alive):
+    """Uniforms the reference's serial loop consumes at greedy step t of the full enumeration with n_alive live
+    candidates: 2 * 2^t mvndst calls of t variables each."""
+    return n_alive * (2 << t) * draws_per_call(t)
+
+
 def _state6(state):
     return (ctypes.c_int * 6)(*[int(v) for v in state])
 
