@@ -1,5 +1,5 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
-include/ital_adapt.h and include/ital_revoke.h).
+include/ital_adapt.h, include/ital_revoke.h and include/ital_rewhiten.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -215,6 +215,21 @@ REVOKE_SIGNATURES = {
 }
 
 
+class ItalRewhitenDesc(ctypes.Structure):
+    """ital_rewhiten_desc (include/ital_rewhiten.h): a range of data rows and the labelled-set state it is whitened against."""
+    _fields_ = [("X", c_void_p), ("n_rows", c_int64), ("ldx", c_int), ("XT", c_void_p), ("XTn", c_void_p), ("L", c_void_p),
+                ("ldl", c_int), ("alpha", c_void_p), ("m", c_int), ("var", c_double), ("length_scale", c_double),
+                ("xnorm", c_void_p), ("V", c_void_p), ("ldv", c_int64), ("v_rows", c_int), ("mu", c_void_p), ("s2", c_void_p),
+                ("chunk", c_int)]
+
+
+#: whitening a range of data rows against the whole labelled set, declared in include/ital_rewhiten.h
+REWHITEN_SIGNATURES = {
+    "ital_whiten_rows": (c_int, [ctypes.POINTER(ItalRewhitenDesc), c_void_p]),
+    "ital_whiten_rows_chunk": (c_int, []),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -234,7 +249,7 @@ def load(path=LIB_PATH):
         pass
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
-            list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()):
+            list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -48,6 +48,12 @@ class AdaptAL(ActiveRetrievalBase):
         #: what the last fetch computed (numpy): candidates, entropy, density, max_ind, error vector (None: early return)
         self.last = None
 
+    def _start_afresh(self):
+        """add_data() / set_params(): the block, Gram and error buffers start afresh."""
+        ActiveRetrievalBase._start_afresh(self)
+        self._block_bufs = self._gram_bufs = self._err_bufs = None
+        self.last = None
+
     _gather_block = MCMI_min._gather_block      # the replicated candidate block, kept between fetches of one shape
 
     def _gram_buffers(self, nc, ldc, work_len):

@@ -377,6 +377,93 @@ class GaussianProcess(object):
         self._replicate_mean()
         return self
 
+    # ------------------------------------------------------------------ a live session: more rows, other hyper-parameters
+    def _whiten_rows(self, row_start, n_rows):
+        """xnorm, V[0:m], mu, s2 of the local rows [row_start, row_start + n_rows) against the whole current labelled set
+        (ital_whiten_rows: the feature rows are read ceil(m / chunk) times, not ceil(m / 16) times); rows m .. cap of V zero."""
+        r = _lib.ItalRewhitenDesc()
+        r.X, r.n_rows, r.ldx = self.Xd.data_ptr() + 8 * row_start * self.ldx, n_rows, self.ldx
+        r.XT, r.XTn, r.L, r.ldl, r.alpha, r.m = _ptr(self.XT), _ptr(self.XTn), _ptr(self.L), self.cap, _ptr(self.alpha), self.m
+        r.var, r.length_scale = float(self.var), float(self.length_scale)
+        r.xnorm, r.V, r.ldv, r.v_rows = self.xnorm.data_ptr() + 8 * row_start, self.V.data_ptr() + 8 * row_start, self.ldv, self.cap
+        r.mu, r.s2, r.chunk = self.mu.data_ptr() + 8 * row_start, self.s2.data_ptr() + 8 * row_start, 0
+        check(self._lib.ital_whiten_rows(ctypes.byref(r), _stream()))
+
+    def extend(self, rows):
+        """Appends samples to the data matrix of a live model: they get the indices n_total .. n_total + len(rows) - 1.  The
+        buffers indexed by row (Xd, xnorm, V with its new leading dimension, mu, s2) grow by device-to-device copies -- no
+        feature of an existing row is uploaded again, none of their whitened columns recomputed -- and the new range alone
+        is whitened against the labelled set (ital_whiten_rows).  Queries are labelled rows numbered from n_total on: their
+        entries of `ind` move up by len(rows).  The reference has no such call: its dense K_all (gp.py:128) is built once.
+
+        An empty array is a no-op; ValueError (nothing changed) for another number of columns; NotImplementedError on
+        several ranks: row sharding cannot grow yet."""
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.size == 0:
+            return self
+        if rows.ndim != 2 or rows.shape[1] != self.d:
+            raise ValueError("rows must be a k-by-%d array" % self.d)
+        if self.world > 1 or not isinstance(self.X_host, np.ndarray):
+            raise NotImplementedError("row sharding cannot grow yet: extend() needs all rows on one rank")
+        k, n_old, m, dev = len(rows), self.n, self.m, self.device
+        n_new = n_old + k
+        ldv = _pad16(n_new)
+        with torch.cuda.device(dev):
+            Xd = torch.zeros((n_new, self.ldx), dtype=torch.float64, device=dev)
+            Xd[:n_old] = self.Xd[:n_old]
+            Xd[n_old:, : self.d] = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+            xnorm = torch.empty(n_new, dtype=torch.float64, device=dev)
+            mu = torch.empty(n_new, dtype=torch.float64, device=dev)
+            s2 = torch.empty(n_new, dtype=torch.float64, device=dev)
+            V = torch.zeros((self.cap, ldv), dtype=torch.float64, device=dev)
+            xnorm[:n_old], mu[:n_old], s2[:n_old] = self.xnorm[:n_old], self.mu[:n_old], self.s2[:n_old]
+            if m and n_old:
+                V[:m, :n_old] = self.V[:m, :n_old]
+            self.Xd, self.xnorm, self.mu, self.s2, self.V = Xd, xnorm, mu, s2, V
+            self.n, self.ldv = n_new, ldv
+            self.ind = [i + k if i >= self.n_total else i for i in self.ind]
+            self.n_total += k
+            self.row1 = self.row0 + n_new
+            self.X_host = np.concatenate((self.X_host, rows))
+            self._append_desc = None          # it holds X, xnorm, n and ldv
+            self._gather_bufs = {}
+            self._whiten_rows(n_old, k)
+            self._replicate_mean()
+        return self
+
+    def set_params(self, length_scale=None, var=None, noise=None):
+        """Other kernel hyper-parameters for a live model (None: as it is), e.g. what ital_amd.tune found: the factor and alpha
+        are built anew in fresh buffers (ital_chol_append over the stored XT, y in blocks of 16) and, once the status word
+        says the Gram was positive definite, swapped in; every local row is then whitened again (ital_whiten_rows) and the
+        means replicated -- every rank makes the same call.  LinAlgError leaves the model exactly as it was.  What the
+        parent offered instead: set the attributes and fit(ind, y), i.e. ceil(m/16) sweeps over X and V."""
+        ls = float(self.length_scale if length_scale is None else length_scale)
+        var = float(self.var if var is None else var)
+        noise = float(self.noise if noise is None else noise)
+        if not (ls > 0 and var > 0):
+            raise ValueError("length_scale and var must be positive")
+        with torch.cuda.device(self.device):
+            if self.m == 0:
+                self.s2.fill_(var)
+            else:
+                lib, st, m = self._lib, _stream(), self.m
+                L = torch.zeros((self.cap, self.cap), dtype=torch.float64, device=self.device)
+                alpha = torch.zeros(self.cap, dtype=torch.float64, device=self.device)
+                status = torch.zeros(1, dtype=torch.int32, device=self.device)
+                yd = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(self.device)
+                for c0 in range(0, m, 16):
+                    c = min(16, m - c0)
+                    check(lib.ital_chol_append(_ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(L), self.cap, _ptr(alpha),
+                                               _ptr(yd[c0:c0 + c]), c0, c, var, ls, noise, _ptr(status), st))
+                self.check_status(int(status.item()))
+                self.L, self.alpha = L, alpha
+                self._append_desc = None      # it holds L and alpha
+            self.length_scale, self.length_scale_sq, self.var, self.noise = ls, ls * ls, var, noise
+            if self.m:
+                self._whiten_rows(0, self.n)
+                self._replicate_mean()
+        return self
+
     def check_status(self, status=None):
         """Raises if a kernel flagged a numerical failure.  `status`: the word as already downloaded (e.g. the OR over all
         ranks that the selection step returns); otherwise this rank's word is read (synchronises).  Bit 1 comes from the

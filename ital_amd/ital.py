@@ -169,6 +169,17 @@ class ITAL(ActiveRetrievalBase):
         self._round_bufs = None
         return b
 
+    def _start_afresh(self):
+        """add_data() / set_params(): the batch buffers (keyed by the row count's ldv), the device's candidate list and the
+        prepared next round start afresh."""
+        ActiveRetrievalBase._start_afresh(self)
+        if self._round_bufs is not None:
+            self._round_bufs.drop_prepared()
+            self._round_bufs.invalidate()
+        self._fetch_bufs = None
+        self._round_bufs = None
+        self._ce_subset = None
+
     @property
     def _dev_list(self):
         """The candidate list the device holds (_fast_round.DeviceList); None unless the next round may follow it."""

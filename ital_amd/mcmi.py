@@ -67,6 +67,13 @@ class MCMI_min(ActiveRetrievalBase):
     def candidates(self, value):
         self._candidates = value
 
+    def _start_afresh(self):
+        """add_data() / set_params(): the candidates of the last fetch and the block and fetch buffers start afresh."""
+        ActiveRetrievalBase._start_afresh(self)
+        self.candidates = []
+        self._block_bufs = None
+        self._fetch_bufs = None
+
     def _mark(self, stage=None, t=0, size=0, start=None):
         if self.profile is None:
             return None

@@ -328,6 +328,40 @@ class ActiveRetrievalBase(object):
         self.__dict__["_unseen"] = None
         self._fitted = self.gp.m > 0
 
+    def _start_afresh(self):
+        """What a learner derives from the data matrix or the hyper-parameters and keeps between rounds -- the cached list of
+        unseen samples, the batch state of the last fetch, device buffers sized by the number of rows -- is dropped and built
+        again on its next use.  The derived learners add their own."""
+        self.__dict__["_unseen"] = None
+        self._last_batch = None
+
+    def add_data(self, rows):
+        """Appends samples to a live session (GaussianProcess.extend): the new ones get the ids len(data) .. and are unseen;
+        feedback, `rounds` and both random streams stay as they are.  The reference would need a new learner (and a new
+        dense K_all, gp.py:128).  An empty array is a no-op; ValueError (nothing changed) for another number of columns;
+        NotImplementedError on several ranks: row sharding cannot grow yet."""
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.size == 0:
+            return self
+        if rows.ndim != 2 or rows.shape[1] != np.shape(self.data)[1]:
+            raise ValueError("rows must be a k-by-%d array" % np.shape(self.data)[1])
+        if self.world > 1:
+            raise NotImplementedError("row sharding cannot grow yet: add_data() needs all rows on one rank")
+        self.gp.extend(rows)
+        self.data = self.gp.X_host
+        self._start_afresh()
+        return self
+
+    def set_params(self, length_scale=None, var=None, noise=None):
+        """Other kernel hyper-parameters for a live session (None: as it is), e.g. the result of ital_amd.tune
+        (GaussianProcess.set_params: the factor is built anew and every row whitened again in one pass per chunk of labelled
+        samples).  LinAlgError for a Gram that is not positive definite; the session is then exactly as it was.  Several
+        ranks: every rank makes the same call."""
+        self.gp.set_params(length_scale, var, noise)
+        self.length_scale, self.var, self.noise = self.gp.length_scale, self.gp.var, self.gp.noise
+        self._start_afresh()
+        return self
+
     def relabel(self, feedback):
         """update(feedback) for a user who corrects themselves: the ids of `feedback` whose stored feedback differs from the
         new one are revoked first, then `feedback` is applied as update() applies it.  update() itself keeps refusing a
