@@ -1,5 +1,5 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
-include/ital_adapt.h, include/ital_revoke.h and include/ital_rewhiten.h).
+include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h and include/ital_evidence.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -230,6 +230,25 @@ REWHITEN_SIGNATURES = {
 }
 
 
+class ItalEvidenceDesc(ctypes.Structure):
+    """ital_evidence_desc (include/ital_evidence.h): the labelled set, a chunk of candidates and where their scores go."""
+    _fields_ = [("XT", c_void_p), ("XTn", c_void_p), ("ldx", c_int), ("y", c_void_p), ("m", c_int), ("params", c_void_p),
+                ("G", c_int), ("K", c_void_p), ("ld", c_int64), ("scores", c_void_p), ("info", c_void_p),
+                ("loo_mean", c_void_p), ("loo_var", c_void_p), ("ldm", c_int64), ("status", c_void_p), ("work", c_void_p),
+                ("work_doubles", c_int64), ("ev", c_void_p)]
+
+
+#: GP evidence and leave-one-out scores of many hyper-parameter candidates, declared in include/ital_evidence.h
+EVIDENCE_SIGNATURES = {
+    "ital_gram_grid": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "ital_chol_inv_diag_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                           c_void_p]),
+    "ital_chol_inv_diag_batched_workspace": (c_int64, [c_int, c_int]),
+    "ital_gp_evidence": (c_int, [ctypes.POINTER(ItalEvidenceDesc), c_void_p]),
+    "ital_gp_evidence_workspace": (c_int64, [c_int, c_int]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -249,7 +268,8 @@ def load(path=LIB_PATH):
         pass
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
-            list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()):
+            list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
+            list(EVIDENCE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

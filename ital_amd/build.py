@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libital_hip.so")
-SOURCES = ["api.hip", "rbf.hip", "chol.hip", "score.hip", "select.hip", "mcmi.hip", "score_generic.hip", "gen_pipeline.hip", "topk.hip", "exchange.hip", "round.hip", "ctx.hip", "dense.hip", "adapt.hip", "revoke.hip", "rewhiten.hip",
+SOURCES = ["api.hip", "rbf.hip", "chol.hip", "score.hip", "select.hip", "mcmi.hip", "score_generic.hip", "gen_pipeline.hip", "topk.hip", "exchange.hip", "round.hip", "ctx.hip", "dense.hip", "adapt.hip", "revoke.hip", "rewhiten.hip", "evidence.hip",
            "mvn_stream.cpp", "np_legacy.cpp"]    # .cpp: host-only translation units (no HIP), also built by tools/asan_host.sh
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXTRA = os.environ.get("ITAL_HIPCC_EXTRA", "").split()          # added to every .hip compile (kernel-variant experiments)
@@ -31,7 +31,8 @@ def _newer(target, deps):
 def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
               [os.path.join(INCLUDE, "ital_hip.h"), os.path.join(INCLUDE, "ital_ctx.h"), os.path.join(INCLUDE, "ital_dense.h"),
-               os.path.join(INCLUDE, "ital_adapt.h"), os.path.join(INCLUDE, "ital_revoke.h"), os.path.join(INCLUDE, "ital_rewhiten.h")]
+               os.path.join(INCLUDE, "ital_adapt.h"), os.path.join(INCLUDE, "ital_revoke.h"), os.path.join(INCLUDE, "ital_rewhiten.h"),
+               os.path.join(INCLUDE, "ital_evidence.h")]
     objdir = os.environ.get("ITAL_OBJ_DIR", os.path.join(HERE, "_obj"))
     os.makedirs(objdir, exist_ok=True)
     jobs = []

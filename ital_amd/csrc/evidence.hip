@@ -1,0 +1,404 @@
+// Scoring many hyper-parameter candidates against the labelled set of a live session (include/ital_evidence.h;
+// GaussianProcess.evidence, tune.session_scores, ActiveRetrievalBase.tune_params): the log marginal likelihood and the
+// closed-form leave-one-out quantities of Rasmussen & Williams (2.30), (5.10), (5.12) for G candidates at once.
+//
+//   ital_gram_grid              lower triangles of G Grams from one set of feature dot products per workgroup
+//   ital_chol_inv_diag_batched  (K_g^-1)_ii = sum_{j >= i} (L_g^-1)[j][i]^2 of G factors, one workgroup per matrix
+//   ital_gp_evidence            setup, Gram grid, ital_chol_batched, ital_chol_solve_batched, inverse diagonals, reduction
+//
+// The Gram tile is the 128 x 128 LDS-staged v_mfma_f64_16x16x4_f64 tile of dense.hip, restated here (dense.hip and the units
+// tools/stamp.py hashes stay as they are); the Cholesky and the solves are dense.hip's own entry points.  Every sum has a
+// fixed order and no kernel lets one matrix see another: a candidate gets the same bits alone or in any batch.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "ital_evidence.h"
+#include "ital_internal.h"
+
+namespace ital {
+namespace evidence {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int T = 128;         // output tile edge of the Gram kernel
+constexpr int KS = 16;         // k-elements per LDS stage
+constexpr int LDT = T + 4;     // padded row stride of a staged tile (doubles)
+constexpr int CH = 1024;       // columns of a factor row staged per step of the inverse-diagonal kernel
+constexpr int64_t GRID_TARGET_BLOCKS = 512;   // workgroups the Gram grid aims at: 256 CUs x 2
+
+typedef double StageLds[2][2][KS][LDT];   // [buffer][A / B][k][row]
+
+// Lower-triangular tile pair (ti >= tj) of a linear block index t = ti (ti + 1) / 2 + tj.
+__device__ inline void tri_pair(int64_t t, int& ti, int& tj) {
+    int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((int64_t)(r + 1) * (r + 2) / 2 <= t) r++;
+    while ((int64_t)r * (r + 1) / 2 > t) r--;
+    ti = r;
+    tj = (int)(t - (int64_t)r * (r + 1) / 2);
+}
+
+// Staging role of a thread: k-pair sk, sk + 1 of the tile rows srow + 8 u, u = 0..3.
+__device__ inline void stage_role(int& sk, int& srow) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    sk = 2 * ((lane & 3) + 4 * (lane >> 5));
+    srow = 32 * wave + ((lane >> 2) & 7);
+}
+
+// acc[p][q] += sum_k A_r[k] B_c[k] over k < K (a multiple of KS) for the 128 x 128 tile of a workgroup of 256 threads: wave
+// (wy, wx) owns rows 64 wy + 16 p + (kg + 4 reg) of A and columns 64 wx + 16 q + col of B (D layout of the f64 MFMA).
+// pa[u] / pb[u]: this thread's staged rows srow + 8 u of A / B, already offset by sk.  Register + LDS double buffer, one
+// barrier per stage; ends with a barrier.
+__device__ inline void tile_nt(const double* const pa[4], const double* const pb[4], int K, StageLds& lds, d4 acc[4][4]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, kg = lane >> 4;
+    const int wy = wave >> 1, wx = wave & 1;
+    int sk, srow;
+    stage_role(sk, srow);
+    double2 ra[4], rb[4];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            ra[u].x = pa[u][k0];
+            ra[u].y = pa[u][k0 + 1];
+            rb[u].x = pb[u][k0];
+            rb[u].y = pb[u][k0 + 1];
+        }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            lds[buf][0][sk][srow + 8 * u] = ra[u].x;
+            lds[buf][0][sk + 1][srow + 8 * u] = ra[u].y;
+            lds[buf][1][sk][srow + 8 * u] = rb[u].x;
+            lds[buf][1][sk + 1][srow + 8 * u] = rb[u].y;
+        }
+    };
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    const int nstep = K / KS;
+    for (int s_ = 0; s_ < nstep; s_++) {
+        const int buf = s_ & 1;
+        if (s_ + 1 < nstep) fetch((s_ + 1) * KS);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            double av[4], bv[4];
+#pragma unroll
+            for (int p = 0; p < 4; p++) av[p] = lds[buf][0][4 * kg + j][64 * wy + 16 * p + col];
+#pragma unroll
+            for (int q = 0; q < 4; q++) bv[q] = lds[buf][1][4 * kg + j][64 * wx + 16 * q + col];
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[p], bv[q], acc[p][q], 0, 0, 0);
+        }
+        if (s_ + 1 < nstep) stage(buf ^ 1);
+        __syncthreads();
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------- Gram grid
+struct GridArgs {
+    const double* XT; const double* xn; int m; int ldx;
+    const double* params; int G;
+    double* K; int64_t ld;
+};
+
+// grid: (lower tile pairs, groups of candidates).  The tile's squared distances are formed once; candidate g = blockIdx.y,
+// blockIdx.y + gridDim.y, ... each run their own epilogue over them.
+__global__ __launch_bounds__(256, 2) void gram_grid_kernel(GridArgs a) {
+    __shared__ StageLds lds;
+    const int64_t m = a.m;
+    int ti, tj;
+    tri_pair(blockIdx.x, ti, tj);
+    const int64_t i0 = (int64_t)ti * T, j0 = (int64_t)tj * T;
+    if (i0 >= m) return;
+    int sk, srow;
+    stage_role(sk, srow);
+    const double* pa[4];
+    const double* pb[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {     // rows past m: the last row (computed, never stored)
+        pa[u] = a.XT + min(i0 + srow + 8 * u, m - 1) * a.ldx + sk;
+        pb[u] = a.XT + min(j0 + srow + 8 * u, m - 1) * a.ldx + sk;
+    }
+    d4 acc[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[p][q] = (d4){0, 0, 0, 0};
+    tile_nt(pa, pb, a.ldx, lds, acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, kg = lane >> 4;
+    const int64_t iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
+    // D = |x_i|^2 + |x_j|^2 - 2 x_i . x_j in place (the expansion of ital_gram_rows; not clamped)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const double bnj = a.xn[min(jw + 16 * q + col, m - 1)];
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const double ani = a.xn[min(iw + 16 * p + kg + 4 * reg, m - 1)];
+                acc[p][q][reg] = ani + bnj - 2 * acc[p][q][reg];
+            }
+    }
+    for (int g = blockIdx.y; g < a.G; g += gridDim.y) {
+        const double l = a.params[3 * (int64_t)g], var = a.params[3 * (int64_t)g + 1], noise = a.params[3 * (int64_t)g + 2];
+        const double s = -2.0 * l * l;
+        double* K = a.K + (int64_t)g * m * a.ld;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int64_t j = jw + 16 * q + col;
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                // a 16 x 16 sub-tile with nothing at or below the diagonal inside the matrix: the whole wave skips it
+                if (iw + 16 * p >= m || jw + 16 * q > iw + 16 * p + 15) continue;
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    const int64_t i = iw + 16 * p + kg + 4 * reg;
+                    double v = var * exp(acc[p][q][reg] / s);
+                    if (i == j) v += noise;
+                    if (i < m && j <= i) K[i * a.ld + j] = v;
+                }
+            }
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------- inverse diagonals
+struct InvdArgs {
+    const double* const* L; const int64_t* ld; int n; const int* info;
+    double* out; int64_t ldo;
+    double* work;          // M = L^-1 of matrix g at work + g n n, row-major [j][i], lower triangle
+};
+
+// One workgroup per matrix.  Column i of M belongs to thread i % 256 alone: it writes M[j][i] row by row and is the only
+// one to read it again, so the only data shared between threads is the staged row of L (double-buffered: one barrier per
+// staged piece).  A row longer than CH is taken in pieces; a column's partial sum then waits in M[j][i] itself.  Within a
+// wave the k-loop starts at the wave's first column, so that at every step the lanes read neighbouring elements of one row
+// of M; a lane joins at k = i.
+__global__ __launch_bounds__(256) void inv_diag_batched_kernel(InvdArgs a) {
+    __shared__ double lrow[2][CH];
+    const int g = blockIdx.x, n = a.n, tid = threadIdx.x;
+    double* out = a.out + (int64_t)g * a.ldo;
+    if (a.info && a.info[g] != 0) {
+        for (int i = tid; i < n; i += 256) out[i] = __builtin_nan("");
+        return;
+    }
+    const double* L = a.L[g];
+    const int64_t ld = a.ld[g];
+    double* M = a.work + (int64_t)g * n * n;
+    int it = 0;
+    for (int j = 0; j < n; j++) {
+        const double* Lj = L + (int64_t)j * ld;
+        double* Mj = M + (int64_t)j * n;
+        const double ljj = Lj[j];
+        for (int c0 = 0; c0 < j; c0 += CH, it++) {
+            const int c1 = min(j, c0 + CH), buf = it & 1;
+            for (int k = c0 + tid; k < c1; k += 256) lrow[buf][k - c0] = Lj[k];
+            __syncthreads();
+            for (int i = tid; i < c1; i += 256) {
+                double acc = i >= c0 ? 0.0 : Mj[i];
+                const int kb = max(c0, i & ~63);
+                const double* Mk = M + (int64_t)kb * n + i;
+#pragma unroll 4
+                for (int k = kb; k < c1; k++, Mk += n)
+                    if (k >= i) acc += lrow[buf][k - c0] * *Mk;
+                Mj[i] = c1 == j ? -acc / ljj : acc;
+            }
+        }
+        if (tid == (j & 255)) Mj[j] = 1.0 / ljj;
+    }
+    for (int i = tid; i < n; i += 256) {
+        double ss = 0.0;
+        const int jb = i & ~63;
+        const double* Mk = M + (int64_t)jb * n + i;
+        for (int j = jb; j < n; j++, Mk += n)
+            if (j >= i) {
+                const double v = *Mk;
+                ss += v * v;
+            }
+        out[i] = ss;
+    }
+}
+
+// --------------------------------------------------------------------------------------------- setup and the reduction
+struct Layout {          // of the workspace of ital_gp_evidence, in doubles from its start
+    int64_t alpha, cdiag, M, Kp, yp, ldv, nv, total;
+};
+
+__host__ __device__ inline Layout layout(int64_t m, int64_t G) {
+    Layout w;
+    w.alpha = 0;
+    w.cdiag = w.alpha + G * m;
+    w.M = w.cdiag + G * m;
+    w.Kp = w.M + G * m * m;
+    w.yp = w.Kp + G;
+    w.ldv = w.yp + G;
+    w.nv = w.ldv + G;
+    w.total = w.nv + G;      // n as int: half of it used
+    return w;
+}
+
+struct EvArgs {
+    const double* y; int m; int G;
+    double* K; int64_t ld;
+    double* scores; const int* info; double* loo_mean; double* loo_var; int64_t ldm;
+    double* work;
+};
+
+// Workgroup g: the entries of the batched calls' argument arrays for candidate g, and y as the solve's right-hand side.
+__global__ __launch_bounds__(256) void evidence_setup_kernel(EvArgs a) {
+    const int g = blockIdx.x;
+    const Layout w = layout(a.m, a.G);
+    double* alpha = a.work + w.alpha + (int64_t)g * a.m;
+    if (threadIdx.x == 0) {
+        ((double**)(a.work + w.Kp))[g] = a.K + (int64_t)g * a.m * a.ld;
+        ((double**)(a.work + w.yp))[g] = alpha;
+        ((int64_t*)(a.work + w.ldv))[g] = a.ld;
+        ((int*)(a.work + w.nv))[g] = a.m;
+    }
+    for (int i = threadIdx.x; i < a.m; i += 256) alpha[i] = a.y[i];
+}
+
+// Workgroup g: loo_mean, loo_var and the four sums of candidate g.  The terms of 256 samples at a time are formed by all
+// threads, then four threads add one kind each, i ascending.
+__global__ __launch_bounds__(256) void evidence_reduce_kernel(EvArgs a) {
+    __shared__ double term[4][256];
+    const int g = blockIdx.x, m = a.m, tid = threadIdx.x;
+    double* lm = a.loo_mean + (int64_t)g * a.ldm;
+    double* lv = a.loo_var + (int64_t)g * a.ldm;
+    double* sc = a.scores + 3 * (int64_t)g;
+    if (a.info[g] != 0) {
+        for (int i = tid; i < m; i += 256) lm[i] = lv[i] = __builtin_nan("");
+        if (tid == 0) {
+            sc[0] = sc[1] = -__builtin_inf();
+            sc[2] = __builtin_inf();
+        }
+        return;
+    }
+    const Layout w = layout(m, a.G);
+    const double* alpha = a.work + w.alpha + (int64_t)g * m;
+    const double* cd = a.work + w.cdiag + (int64_t)g * m;
+    const double* L = a.K + (int64_t)g * m * a.ld;
+    const double log2pi = 1.8378770664093454836;
+    double sum = 0.0;          // threads 0..3: y.alpha, sum log L_ii, loo_logp, sum (alpha / c)^2
+    for (int i0 = 0; i0 < m; i0 += 256) {
+        const int i = i0 + tid;
+        if (i < m) {
+            const double yi = a.y[i], al = alpha[i], c = cd[i];
+            const double r = al / c, mean = yi - r, var = 1.0 / c, d = yi - mean;
+            lm[i] = mean;
+            lv[i] = var;
+            term[0][tid] = yi * al;
+            term[1][tid] = log(L[(int64_t)i * a.ld + i]);
+            term[2][tid] = -0.5 * log(var) - d * d / (2.0 * var) - 0.5 * log2pi;
+            term[3][tid] = r * r;
+        }
+        __syncthreads();
+        if (tid < 4) {
+            const int cnt = min(256, m - i0);
+            for (int e = 0; e < cnt; e++) sum += term[tid][e];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) term[0][0] = sum;
+    if (tid == 1) term[1][0] = sum;
+    __syncthreads();
+    if (tid == 0) sc[0] = -0.5 * term[0][0] - term[1][0] - 0.5 * (double)m * log2pi;
+    if (tid == 2) sc[1] = sum;
+    if (tid == 3) sc[2] = sum / (double)m;
+}
+
+}  // namespace evidence
+}  // namespace ital
+
+using namespace ital::evidence;
+
+static int launch_gram_grid(const double* XT, const double* XTn, int m, int ldx, const double* params, int G, double* K,
+                            int64_t ld, hipStream_t stream) {
+    const int64_t tn = ((int64_t)m + T - 1) / T, pairs = tn * (tn + 1) / 2;
+    int64_t groups = (GRID_TARGET_BLOCKS + pairs - 1) / pairs;
+    groups = groups > G ? G : groups;
+    groups = groups > 65535 ? 65535 : groups;
+    GridArgs a = {XT, XTn, m, ldx, params, G, K, ld};
+    ITAL_LAUNCH(gram_grid_kernel, dim3((unsigned)pairs, (unsigned)groups), dim3(256), 0, stream, a);
+    return ital_check_launch("ital_gram_grid");
+}
+
+extern "C" int ital_gram_grid(const double* XT, const double* XTn, int m, int ldx, const double* params, int G, double* K,
+                              int64_t ld, hipStream_t stream) {
+    if (!XT || !XTn || !params || !K) return ital_fail(-22, "ital_gram_grid: NULL pointer");
+    if (m < 1 || G < 1) return ital_fail(-22, "ital_gram_grid: m and G must be at least 1");
+    if (ldx <= 0 || ldx % 16 != 0) return ital_fail(-22, "ital_gram_grid: ldx must be a positive multiple of 16");
+    if (ld < m) return ital_fail(-22, "ital_gram_grid: ld must be at least m");
+    if (m > (1 << 22)) return ital_fail(-22, "ital_gram_grid: matrix too large");
+    return launch_gram_grid(XT, XTn, m, ldx, params, G, K, ld, stream);
+}
+
+extern "C" int64_t ital_chol_inv_diag_batched_workspace(int n, int count) {
+    if (n < 1 || count < 1) return 0;
+    return (int64_t)count * n * n;
+}
+
+extern "C" int ital_chol_inv_diag_batched(const double* const* L, const int64_t* ld, int n, int count, const int* info,
+                                          double* out, int64_t ldo, double* work, int64_t work_doubles, hipStream_t stream) {
+    if (!L || !ld || !out || !work) return ital_fail(-22, "ital_chol_inv_diag_batched: NULL pointer");
+    if (n < 1 || count < 1) return ital_fail(-22, "ital_chol_inv_diag_batched: n and count must be at least 1");
+    if (ldo < n) return ital_fail(-22, "ital_chol_inv_diag_batched: ldo must be at least n");
+    if (work_doubles < ital_chol_inv_diag_batched_workspace(n, count))
+        return ital_fail(-22, "ital_chol_inv_diag_batched: work smaller than ital_chol_inv_diag_batched_workspace(n, count)");
+    InvdArgs a = {L, ld, n, info, out, ldo, work};
+    ITAL_LAUNCH(inv_diag_batched_kernel, dim3((unsigned)count), dim3(256), 0, stream, a);
+    return ital_check_launch("ital_chol_inv_diag_batched");
+}
+
+extern "C" int64_t ital_gp_evidence_workspace(int m, int G) {
+    if (m < 1 || G < 1) return 0;
+    return layout(m, G).total;
+}
+
+extern "C" int ital_gp_evidence(const ital_evidence_desc* d, hipStream_t stream) {
+    if (!d) return ital_fail(-22, "ital_gp_evidence: NULL descriptor");
+    if (!d->XT || !d->XTn || !d->y || !d->params || !d->K || !d->scores || !d->info || !d->loo_mean || !d->loo_var ||
+        !d->status || !d->work)
+        return ital_fail(-22, "ital_gp_evidence: NULL pointer");
+    if (d->m < 1 || d->G < 1) return ital_fail(-22, "ital_gp_evidence: m and G must be at least 1");
+    if (d->G > 65535) return ital_fail(-22, "ital_gp_evidence: more than 65535 candidates per call");
+    if (d->m > (1 << 22)) return ital_fail(-22, "ital_gp_evidence: matrix too large");
+    if (d->ldx <= 0 || d->ldx % 16 != 0) return ital_fail(-22, "ital_gp_evidence: ldx must be a positive multiple of 16");
+    if (d->ld < d->m) return ital_fail(-22, "ital_gp_evidence: ld must be at least m");
+    if (d->ldm < d->m) return ital_fail(-22, "ital_gp_evidence: ldm must be at least m");
+    const Layout w = layout(d->m, d->G);
+    if (d->work_doubles < w.total)
+        return ital_fail(-22, "ital_gp_evidence: work smaller than ital_gp_evidence_workspace(m, G)");
+    const int m = d->m, G = d->G;
+    auto mark = [&](int k) {
+        return (d->ev && hipEventRecord((hipEvent_t)d->ev[k], stream) != hipSuccess)
+                   ? ital_fail(-5, "ital_gp_evidence: hipEventRecord failed") : 0;
+    };
+    double* const* Kp = (double* const*)(d->work + w.Kp);
+    double* const* yp = (double* const*)(d->work + w.yp);
+    const int64_t* ldv = (const int64_t*)(d->work + w.ldv);
+    const int* nv = (const int*)(d->work + w.nv);
+    EvArgs a = {d->y, m, G, d->K, d->ld, d->scores, d->info, d->loo_mean, d->loo_var, d->ldm, d->work};
+    int rc;
+    ITAL_LAUNCH(evidence_setup_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
+    if ((rc = ital_check_launch("ital_gp_evidence(setup)"))) return rc;
+    if ((rc = mark(0))) return rc;
+    if ((rc = launch_gram_grid(d->XT, d->XTn, m, d->ldx, d->params, G, d->K, d->ld, stream))) return rc;
+    if ((rc = mark(1))) return rc;
+    if ((rc = ital_chol_batched(Kp, nv, ldv, G, m, d->info, d->status, stream))) return rc;
+    if ((rc = mark(2))) return rc;
+    if ((rc = ital_chol_solve_batched(Kp, nv, ldv, yp, G, d->info, stream))) return rc;
+    if ((rc = mark(3))) return rc;
+    InvdArgs v = {Kp, ldv, m, d->info, d->work + w.cdiag, m, d->work + w.M};
+    ITAL_LAUNCH(inv_diag_batched_kernel, dim3((unsigned)G), dim3(256), 0, stream, v);
+    if ((rc = ital_check_launch("ital_gp_evidence(inverse diagonals)"))) return rc;
+    if ((rc = mark(4))) return rc;
+    ITAL_LAUNCH(evidence_reduce_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
+    if ((rc = ital_check_launch("ital_gp_evidence(reduction)"))) return rc;
+    return mark(5);
+}

@@ -464,6 +464,75 @@ class GaussianProcess(object):
                 self._replicate_mean()
         return self
 
+    def evidence_chunk(self, max_bytes=1 << 30):
+        """Candidates evidence() sends to the device at once so that their Grams, workspace and outputs stay below
+        `max_bytes` (at most 65535, the limit of one ital_gp_evidence call); MemoryError if one candidate alone exceeds it."""
+        m = self.m
+        per = 8 * (m * m + int(self._lib.ital_gp_evidence_workspace(m, 1)) + 2 * m + 4)
+        if per > max_bytes:
+            raise MemoryError("one candidate at m = %d takes %d bytes, more than max_bytes = %d" % (m, per, max_bytes))
+        return int(min(max_bytes // per, 65535))
+
+    def evidence(self, params_list, *, max_bytes=1 << 30, events=None):
+        """Scores hyper-parameter candidates against the model's own labelled set (queries included), without touching the
+        model: for each dict of `params_list` (`length_scale`, optional `var` / `noise`; default: the model's current value)
+        the log marginal likelihood and the closed-form leave-one-out quantities of include/ital_evidence.h.  Returns a dict
+        of numpy arrays: `lml`, `loo_logp`, `loo_mse` [G], `ok` [G] bool (the candidate's Gram was positive definite;
+        otherwise -inf, -inf, +inf and NaN rows), `loo_mean`, `loo_var` [G, m].
+
+        The candidates go to the device in chunks whose Grams and workspace stay below `max_bytes` (ital_gp_evidence: a
+        number of launches that does not depend on the chunk); a candidate's values do not depend on the chunking.  Reads
+        XT, XTn and y and writes buffers of its own: L, alpha, V, mu, s2, the status word and both random streams stay as
+        they are.  Every rank computes the same thing locally: no collective.  RuntimeError for an unfitted model,
+        ValueError for a non-positive length_scale / var, MemoryError if one candidate alone exceeds max_bytes.
+        `events`: None, or six recorded torch events that bracket the five stages of the LAST chunk (tools/evidence_bench.py)."""
+        if self.m == 0:
+            raise RuntimeError("the GP has not been fitted")
+        prm = np.empty((len(params_list), 3), dtype=np.float64)
+        for g, p in enumerate(params_list):
+            unknown = set(p) - {"length_scale", "var", "noise"}
+            if unknown:
+                raise TypeError("unexpected GP parameters: %s" % ", ".join(sorted(unknown)))
+            prm[g] = (float(p.get("length_scale", self.length_scale)), float(p.get("var", self.var)),
+                      float(p.get("noise", self.noise)))
+            if not (prm[g, 0] > 0 and prm[g, 1] > 0):
+                raise ValueError("length_scale and var must be positive")
+        G, m, lib, dev = len(prm), self.m, self._lib, self.device
+        out = dict(lml=np.empty(G), loo_logp=np.empty(G), loo_mse=np.empty(G), ok=np.zeros(G, dtype=bool),
+                   loo_mean=np.empty((G, m)), loo_var=np.empty((G, m)))
+        if G == 0:
+            return out
+        chunk = min(G, self.evidence_chunk(max_bytes))
+        with torch.cuda.device(dev):
+            yd = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(dev)
+            pd = torch.from_numpy(prm).to(dev)
+            K = torch.empty(chunk * m * m, dtype=torch.float64, device=dev)
+            need = int(lib.ital_gp_evidence_workspace(m, chunk))
+            work = torch.empty(need, dtype=torch.float64, device=dev)
+            scores = torch.empty((chunk, 3), dtype=torch.float64, device=dev)
+            info = torch.empty(chunk, dtype=torch.int32, device=dev)
+            lm = torch.empty((chunk, m), dtype=torch.float64, device=dev)
+            lv = torch.empty((chunk, m), dtype=torch.float64, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)      # the call's own word: the model's is not touched
+            d = _lib.ItalEvidenceDesc()
+            d.XT, d.XTn, d.ldx, d.y, d.m = _ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(yd), m
+            d.K, d.ld, d.scores, d.info, d.loo_mean, d.loo_var, d.ldm = _ptr(K), m, _ptr(scores), _ptr(info), _ptr(lm), _ptr(lv), m
+            d.status, d.work, d.work_doubles = _ptr(status), _ptr(work), need
+            for g0 in range(0, G, chunk):
+                c = min(chunk, G - g0)
+                d.params, d.G = pd.data_ptr() + 24 * g0, c
+                ev = None
+                if events is not None and g0 + c == G:
+                    ev = (ctypes.c_void_p * 6)(*[e.cuda_event for e in events])
+                d.ev = ctypes.addressof(ev) if ev is not None else None
+                check(lib.ital_gp_evidence(ctypes.byref(d), _stream()))
+                sc = scores[:c].cpu().numpy()         # synchronises: the chunk's buffers are free again
+                out["lml"][g0:g0 + c], out["loo_logp"][g0:g0 + c], out["loo_mse"][g0:g0 + c] = sc[:, 0], sc[:, 1], sc[:, 2]
+                out["ok"][g0:g0 + c] = info[:c].cpu().numpy() == 0
+                out["loo_mean"][g0:g0 + c] = lm[:c].cpu().numpy()
+                out["loo_var"][g0:g0 + c] = lv[:c].cpu().numpy()
+        return out
+
     def check_status(self, status=None):
         """Raises if a kernel flagged a numerical failure.  `status`: the word as already downloaded (e.g. the OR over all
         ranks that the selection step returns); otherwise this rank's word is read (synchronises).  Bit 1 comes from the

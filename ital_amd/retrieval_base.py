@@ -11,6 +11,7 @@ below them (GP state, candidate bookkeeping, the device path) is this package's 
 """
 import numpy as np
 
+from . import tune
 from .gp import GaussianProcess
 
 
@@ -361,6 +362,20 @@ class ActiveRetrievalBase(object):
         self.length_scale, self.var, self.noise = self.gp.length_scale, self.gp.var, self.gp.noise
         self._start_afresh()
         return self
+
+    def tune_params(self, grid=tune.default_grids['ls_only'], criterion='lml', apply=True, verbose=0):
+        """Finds kernel hyper-parameters for a live session from its own labels (tune.optimize_session_params: alternating
+        grid search over `grid`, every sweep scored on the device by `criterion` -- 'lml', 'loo_logp', 'loo_mse' or 'loo_ap',
+        see tune.session_scores) and, with `apply`, makes them the session's (set_params).  The reference can only tune
+        offline against the ground truth of the whole data set (optimize_parameters.py).  Returns (best parameters, their
+        score).  LinAlgError when no candidate's Gram is positive definite; the session is then exactly as it was.
+        `rounds` and both random streams stay as they are.  Several ranks: every rank makes the same call."""
+        best, score = tune.optimize_session_params(self, grid, criterion=criterion, verbose=verbose)
+        if score == -np.inf:
+            raise np.linalg.LinAlgError("no candidate of the grid has a positive definite kernel matrix of the labelled samples")
+        if apply:
+            self.set_params(**best)
+        return best, score
 
     def relabel(self, feedback):
         """update(feedback) for a user who corrects themselves: the ids of `feedback` whose stored feedback differs from the

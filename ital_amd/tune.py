@@ -288,20 +288,30 @@ def optimize_gp_params(dataset, relevance, grid=default_grids['full'], init=defa
 
     All values of the parameter being swept are cross-validated in one device batch; the lines of `verbose` > 1 are
     printed in grid order."""
+    cache = {}
+    best_params, best_perf = _alternating_search(
+        grid, init, lambda cv_list: _evaluate(dataset, relevance, cv_list, n_folds, fewshot, device, max_bytes, cache), verbose)
+    return best_params, best_perf if relevance is not None else -best_perf
+
+
+def _alternating_search(grid, init, evaluate, verbose):
+    """The control flow of the reference's optimize_gp_params (optimize_parameters.py:121-170): one parameter of `grid` is
+    swept at a time, the others held at their current values (at first `init`'s), until a sweep changes nothing or makes
+    things worse.  `evaluate(list of dicts)` gives their performances, higher is better; ties go to the first best value in
+    grid order.  Returns (dict of the best values, their performance)."""
     param_names = list(grid.keys())
     cur_params = [init[p] for p in param_names]
     changed = [True] * len(param_names)
     changing_param = 0
     perf = {}
     best_perf = -np.inf
-    cache = {}
 
     while any(changed):
 
         values = list(grid[param_names[changing_param]])
         cv_list = [{param_names[i]: val if i == changing_param else cur_params[i] for i in range(len(param_names))}
                    for val in values]
-        results = _evaluate(dataset, relevance, cv_list, n_folds, fewshot, device, max_bytes, cache)
+        results = evaluate(cv_list)
         cur_perfs = {}
         for val, res in zip(values, results):
             cur_perfs[val] = res
@@ -327,7 +337,68 @@ def optimize_gp_params(dataset, relevance, grid=default_grids['full'], init=defa
             break
 
     best_params = max(perf.keys(), key=lambda p: perf[p])
-    return dict(zip(param_names, best_params)), best_perf if relevance is not None else -best_perf
+    return dict(zip(param_names, best_params)), best_perf
+
+
+# ------------------------------------------------------------------------------------- a live session's own labels
+#: what session_scores can rank candidates by (all: higher is better)
+SESSION_CRITERIA = ('lml', 'loo_logp', 'loo_mse', 'loo_ap')
+
+
+def _session_gp(gp_or_learner):
+    return getattr(gp_or_learner, 'gp', gp_or_learner)
+
+
+def session_scores(gp_or_learner, params_list, criterion='lml'):
+    """Scores hyper-parameter candidates (dicts with `length_scale`, `var`, `noise`; what is missing is the session's current
+    value) against the labelled samples of a live session -- a GaussianProcess or a learner -- on the device
+    (GaussianProcess.evidence, include/ital_evidence.h).  No ground truth is needed: the session's own m labels are all
+    there is.  Returns a list of floats, higher is better:
+
+    - 'lml': log marginal likelihood (Rasmussen & Williams 2.30);
+    - 'loo_logp': leave-one-out log predictive probability (5.10);
+    - 'loo_mse': minus the mean squared leave-one-out residual;
+    - 'loo_ap': average precision of the leave-one-out means against the labels' signs, the reference's criterion
+      (optimize_parameters.py:59) with leave-one-out as the folds; ValueError unless the labels hold both signs.
+
+    A candidate whose Gram is not positive definite scores -inf, with the warning of cross_validate_gp."""
+    if criterion not in SESSION_CRITERIA:
+        raise ValueError('criterion must be one of %s' % ', '.join(SESSION_CRITERIA))
+    params_list = [dict(p) for p in params_list]
+    for prm in params_list:
+        unknown = set(prm) - {'length_scale', 'var', 'noise'}
+        if unknown:
+            raise TypeError('unexpected GP parameters: %s' % ', '.join(sorted(unknown)))
+    gp = _session_gp(gp_or_learner)
+    if criterion == 'loo_ap':
+        from sklearn.metrics import average_precision_score
+        y = np.asarray(gp.y if gp.y is not None else [], dtype=np.float64)
+        if not (np.any(y > 0) and np.any(y <= 0)):
+            raise ValueError("criterion 'loo_ap' needs labels of both signs")
+    ev = gp.evidence(params_list)
+    result = []
+    for g in range(len(params_list)):
+        if not ev['ok'][g]:
+            warnings.warn('Matrix is not positive semi-definite.', stacklevel=2)
+            result.append(-np.inf)
+        elif criterion == 'loo_ap':
+            result.append(float(average_precision_score(y > 0, ev['loo_mean'][g])))
+        elif criterion == 'loo_mse':
+            result.append(-float(ev['loo_mse'][g]))
+        else:
+            result.append(float(ev[criterion][g]))
+    return result
+
+
+def optimize_session_params(gp_or_learner, grid=default_grids['ls_only'], init=None, criterion='lml', verbose=1):
+    """optimize_gp_params for a live session: the same alternating grid search, tie rule and printed lines, scored by
+    session_scores on the session's own labels instead of cross-validation against ground truth.  `init`: where the search
+    starts (None: the session's current parameters); parameters that `grid` does not name stay at the session's values.
+    Returns (dict of the best values, their score) -- what set_params() takes."""
+    gp = _session_gp(gp_or_learner)
+    if init is None:
+        init = {'length_scale': gp.length_scale, 'var': gp.var, 'noise': gp.noise}
+    return _alternating_search(grid, init, lambda cv_list: session_scores(gp_or_learner, cv_list, criterion), verbose)
 
 
 # ------------------------------------------------------------------------------------------------------------------ CLI
