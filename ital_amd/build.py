@@ -28,20 +28,22 @@ def _newer(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def headers():
+    """Every header a unit can include: a change to any of them rebuilds all units."""
+    return [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in sorted(os.listdir(d)) if f.endswith(".h")]
+
+
 def build(force=False, verbose=False):
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-              [os.path.join(INCLUDE, "ital_hip.h"), os.path.join(INCLUDE, "ital_ctx.h"), os.path.join(INCLUDE, "ital_dense.h"),
-               os.path.join(INCLUDE, "ital_adapt.h"), os.path.join(INCLUDE, "ital_revoke.h"), os.path.join(INCLUDE, "ital_rewhiten.h"),
-               os.path.join(INCLUDE, "ital_evidence.h")]
     objdir = os.environ.get("ITAL_OBJ_DIR", os.path.join(HERE, "_obj"))
     os.makedirs(objdir, exist_ok=True)
     jobs = []
     objs = []
+    hdrs = headers()
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         objs.append(o)
-        if force or _newer(o, [s] + headers):
+        if force or _newer(o, [s] + hdrs):
             jobs.append([HIPCC] + (FLAGS if src.endswith(".hip") else HOST_FLAGS + HOST_EXTRA) + ["-c", s, "-o", o])
 
     def run(cmd):

@@ -8,40 +8,35 @@
 // The triangular inverse M = L^-1 is built by recursive doubling: the 64 x 64 diagonal blocks (one wave each, forward
 // substitution in LDS), then for s = 64, 128, ... every pair of neighbouring inverted diagonal blocks of size s,
 // [a0, a0 + s) and [a0 + s, min(a0 + 2 s, n)), gets its off-diagonal block M21 = -M22 (L21 M11) in two launches: T = L21 M11
-// and M21 = -M22 T.  Both products run on v_mfma_f64_16x16x4_f64 through a 128 x 128 LDS-staged tile (the tile of
-// dense.hip with the second operand read k-major and every element behind a predicate, which is what makes the triangular
-// k-ranges and ragged edges exact: nothing outside the computed part of M is ever read).  The squared column sums leave the
-// second product's accumulators as one partial per (64-row block, column); a last kernel adds a column's partials top-down.
+// and M21 = -M22 T.  Both products run on v_mfma_f64_16x16x4_f64 through a 128 x 128 LDS-staged tile (tile_mm below: the LDS
+// layout, schedule and MFMA stage of mfma_tile.h's tile_nt, with the second operand read k-major and every element behind a
+// predicate, which is what makes the triangular k-ranges and ragged edges exact: nothing outside the computed part of M is
+// ever read).  The squared column sums leave the second product's accumulators as one partial per (64-row block, column); a
+// last kernel adds a column's partials top-down.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_math.h"
 #include "ital_adapt.h"
 #include "ital_internal.h"
+#include "mfma_tile.h"
 
 namespace ital {
 namespace adapt {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+using namespace ital::tile;
 
-constexpr int T = 128;         // output tile edge
-constexpr int KS = 16;         // k-elements per LDS stage
-constexpr int LDT = T + 4;     // padded row stride of a staged tile (doubles)
 constexpr int NB = 64;         // diagonal block
-
-typedef double StageLds[2][2][KS][LDT];   // [buffer][A / B][k][row or column]; 66 KB: relies on gfx950's 160 KB of LDS per CU
 
 // acc[p][q] += sum over kbeg <= k < kend of A(r, k) B(k, c) for the 128 x 128 tile of a workgroup of 256 threads: wave
 // (wy, wx) owns tile rows 64 wy + 16 p + (kg + 4 reg) and tile columns 64 wx + 16 q + col (D layout of the f64 MFMA).
 // fa(r, k): element of A at tile row r; fb(k, c): element of B at tile column c; both return 0 outside their operand (k at
-// or past kend included).  A is staged as k-pairs of rows, B as runs of 16 columns of one k.  Register + LDS double buffer,
-// one barrier per stage; ends with a barrier.
+// or past kend included).  A is staged as k-pairs of rows (stage_role), B as runs of 16 columns of one k, into the layout
+// mfma_stage reads.  Register + LDS double buffer, one barrier per stage; ends with a barrier.
 template <class FA, class FB>
 __device__ inline void tile_mm(FA fa, FB fb, int kbeg, int kend, StageLds& lds, d4 acc[4][4]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, kg = lane >> 4;
-    const int wy = wave >> 1, wx = wave & 1;
-    const int ska = 2 * ((lane & 3) + 4 * (lane >> 5)), arow = 32 * wave + ((lane >> 2) & 7);
+    int ska, arow;
+    stage_role(ska, arow);
     const int kb = threadIdx.x >> 4, bcol = threadIdx.x & 15;
     double ra[8], rb[8];
     auto fetch = [&](int k0) {
@@ -70,18 +65,7 @@ __device__ inline void tile_mm(FA fa, FB fb, int kbeg, int kend, StageLds& lds, 
     for (int s_ = 0; s_ < nstep; s_++) {
         const int buf = s_ & 1;
         if (s_ + 1 < nstep) fetch(kbeg + (s_ + 1) * KS);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) av[p] = lds[buf][0][4 * kg + j][64 * wy + 16 * p + col];
-#pragma unroll
-            for (int q = 0; q < 4; q++) bv[q] = lds[buf][1][4 * kg + j][64 * wx + 16 * q + col];
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[p], bv[q], acc[p][q], 0, 0, 0);
-        }
+        mfma_stage(lds, buf, acc);
         if (s_ + 1 < nstep) stage(buf ^ 1);
         __syncthreads();
     }
@@ -139,13 +123,6 @@ __device__ inline bool pair_tile(const InvArgs& a, int& a0, int& c0, int& c1, in
     return i0 < c1;
 }
 
-__device__ inline void zero_acc(d4 acc[4][4]) {
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc[p][q] = (d4){0, 0, 0, 0};
-}
-
 // T[i][j] = sum_{k = j}^{c0 - 1} L[i][k] M[k][j], i in [c0, c1), j in [a0, c0): M11 is lower triangular.
 __global__ __launch_bounds__(256, 2) void inv_lm_kernel(InvArgs a) {
     __shared__ StageLds lds;
@@ -163,17 +140,15 @@ __global__ __launch_bounds__(256, 2) void inv_lm_kernel(InvArgs a) {
     d4 acc[4][4];
     zero_acc(acc);
     tile_mm(fa, fb, j0, c0, lds, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, kg = lane >> 4;
-    const int iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
+    const DLane dl = d_lane();
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const int j = jw + 16 * q + col;
+        const int j = j0 + dl.column(q);
 #pragma unroll
         for (int p = 0; p < 4; p++)
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
-                const int i = iw + 16 * p + kg + 4 * reg;
+                const int i = i0 + dl.row(p, reg);
                 if (i < c1 && j < c0) a.Tm[(int64_t)i * a.ldw + j] = acc[p][q][reg];
             }
     }
@@ -198,18 +173,17 @@ __global__ __launch_bounds__(256, 2) void inv_mt_kernel(InvArgs a) {
     d4 acc[4][4];
     zero_acc(acc);
     tile_mm(fa, fb, c0, min(i0 + T, c1), lds, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, kg = lane >> 4;
-    const int iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
+    const DLane dl = d_lane();
+    const int iw = i0 + 64 * dl.wy;     // first row of the wave's 64-row block
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const int j = jw + 16 * q + col;
+        const int j = j0 + dl.column(q);
         double ss = 0.0;
 #pragma unroll
         for (int p = 0; p < 4; p++)
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
-                const int i = iw + 16 * p + kg + 4 * reg;
+                const int i = i0 + dl.row(p, reg);
                 const double v = -acc[p][q][reg];
                 if (i < c1 && j < c0) {
                     a.M[(int64_t)i * a.ldw + j] = v;
@@ -218,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void inv_mt_kernel(InvArgs a) {
             }
         ss += __shfl_xor(ss, 16, 64);
         ss += __shfl_xor(ss, 32, 64);
-        if (kg == 0 && iw < c1 && j < c0) a.part[(int64_t)(iw / NB) * a.ldw + j] = ss;
+        if (dl.kg == 0 && iw < c1 && j < c0) a.part[(int64_t)(iw / NB) * a.ldw + j] = ss;
     }
 }
 

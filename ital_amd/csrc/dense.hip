@@ -9,101 +9,21 @@
 //
 // Matrices are row-major with their own leading dimension; the factor overwrites the lower triangle (L[i][j], j <= i) and
 // nothing else: the strict upper triangle and the padding past n are never written.  Every product with a k-dimension runs
-// on v_mfma_f64_16x16x4_f64 through the 128 x 128 LDS-staged tile of cov_block_lds_kernel (mcmi.hip); the diagonal blocks
-// (64 x 64, one workgroup each) and the row-wise panel solve are VALU work, a few per cent of the flops.
+// on v_mfma_f64_16x16x4_f64 through the 128 x 128 LDS-staged tile of mfma_tile.h; the diagonal blocks (64 x 64, one workgroup
+// each) and the row-wise panel solve are VALU work, a few per cent of the flops.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ital_dense.h"
 #include "ital_internal.h"
+#include "mfma_tile.h"
 
 namespace ital {
 namespace dense {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+using namespace ital::tile;
 
-constexpr int T = 128;         // output tile edge of the MFMA kernels
-constexpr int KS = 16;         // k-elements per LDS stage
-constexpr int LDT = T + 4;     // padded row stride of a staged tile (doubles)
 constexpr int NB = 64;         // Cholesky block
-
-typedef double StageLds[2][2][KS][LDT];   // [buffer][A / B][k][row]
-
-// Lower-triangular tile pair (ti >= tj) of a linear block index t = ti (ti + 1) / 2 + tj.
-__device__ inline void tri_pair(int64_t t, int& ti, int& tj) {
-    int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((int64_t)(r + 1) * (r + 2) / 2 <= t) r++;
-    while ((int64_t)r * (r + 1) / 2 > t) r--;
-    ti = r;
-    tj = (int)(t - (int64_t)r * (r + 1) / 2);
-}
-
-// Staging role of a thread (as in cov_block_lds_kernel): k-pair sk, sk + 1 of the tile rows srow + 8 u, u = 0..3.
-__device__ inline void stage_role(int& sk, int& srow) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    sk = 2 * ((lane & 3) + 4 * (lane >> 5));
-    srow = 32 * wave + ((lane >> 2) & 7);
-}
-
-// acc[p][q] += sum_k A_r[k] B_c[k] over k < K (a multiple of KS) for the 128 x 128 tile of a workgroup of 256 threads: wave
-// (wy, wx) owns rows 64 wy + 16 p + (kg + 4 reg) of A and columns 64 wx + 16 q + col of B (D layout of the f64 MFMA).
-// pa[u] / pb[u]: this thread's staged rows srow + 8 u of A / B, already offset by sk.  Register + LDS double buffer, one
-// barrier per stage; ends with a barrier, so the caller may reuse `lds`.
-__device__ inline void tile_nt(const double* const pa[4], const double* const pb[4], int K, StageLds& lds, d4 acc[4][4]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, kg = lane >> 4;
-    const int wy = wave >> 1, wx = wave & 1;
-    int sk, srow;
-    stage_role(sk, srow);
-    double2 ra[4], rb[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            ra[u].x = pa[u][k0];
-            ra[u].y = pa[u][k0 + 1];
-            rb[u].x = pb[u][k0];
-            rb[u].y = pb[u][k0 + 1];
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            lds[buf][0][sk][srow + 8 * u] = ra[u].x;
-            lds[buf][0][sk + 1][srow + 8 * u] = ra[u].y;
-            lds[buf][1][sk][srow + 8 * u] = rb[u].x;
-            lds[buf][1][sk + 1][srow + 8 * u] = rb[u].y;
-        }
-    };
-    fetch(0);
-    stage(0);
-    __syncthreads();
-    const int nstep = K / KS;
-    for (int s_ = 0; s_ < nstep; s_++) {
-        const int buf = s_ & 1;
-        if (s_ + 1 < nstep) fetch((s_ + 1) * KS);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) av[p] = lds[buf][0][4 * kg + j][64 * wy + 16 * p + col];
-#pragma unroll
-            for (int q = 0; q < 4; q++) bv[q] = lds[buf][1][4 * kg + j][64 * wx + 16 * q + col];
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[p], bv[q], acc[p][q], 0, 0, 0);
-        }
-        if (s_ + 1 < nstep) stage(buf ^ 1);
-        __syncthreads();
-    }
-}
-
-__device__ inline void zero_acc(d4 acc[4][4]) {
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc[p][q] = (d4){0, 0, 0, 0};
-}
 
 // ---------------------------------------------------------------------------------------------------------------- Gram
 struct GramArgs {
@@ -150,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void gram_kernel(GramArgs a) {
                 const int64_t i = iw + 16 * p + kg + 4 * reg;
                 const double ani = a.xn[idx[min(i, n - 1)]];
                 // reference: K_all = v * exp((A + B - 2 C) / s) (gp.py:412 / dist_kernel :436), then + noise * eye (:158)
-                double v = a.var * exp((ani + bnj - 2 * acc[p][q][reg]) / a.s);
+                double v = a.var * exp(rbf_sqdist(ani, bnj, acc[p][q][reg]) / a.s);
                 if (i == j) v += a.noise;
                 if (i < n && j <= i) K[i * ld + j] = v;
             }
@@ -385,7 +305,7 @@ __global__ __launch_bounds__(256, 2) void kernel_w_kernel(KwArgs a) {
             for (int reg = 0; reg < 4; reg++) {
                 const double bnj = a.bn[min(jw + 16 * p + kg + 4 * reg, a.nb - 1)];
 #pragma unroll
-                for (int q = 0; q < 4; q++) acc[p][q][reg] = a.var * exp((bnj + ani[q] - 2 * acc[p][q][reg]) / a.s);
+                for (int q = 0; q < 4; q++) acc[p][q][reg] = a.var * exp(rbf_sqdist(bnj, ani[q], acc[p][q][reg]) / a.s);
             }
 #pragma unroll
             for (int r = 0; r < 4; r++) {

@@ -6,97 +6,24 @@
 //   ital_chol_inv_diag_batched  (K_g^-1)_ii = sum_{j >= i} (L_g^-1)[j][i]^2 of G factors, one workgroup per matrix
 //   ital_gp_evidence            setup, Gram grid, ital_chol_batched, ital_chol_solve_batched, inverse diagonals, reduction
 //
-// The Gram tile is the 128 x 128 LDS-staged v_mfma_f64_16x16x4_f64 tile of dense.hip, restated here (dense.hip and the units
-// tools/stamp.py hashes stay as they are); the Cholesky and the solves are dense.hip's own entry points.  Every sum has a
-// fixed order and no kernel lets one matrix see another: a candidate gets the same bits alone or in any batch.
+// The Gram tile is the 128 x 128 LDS-staged v_mfma_f64_16x16x4_f64 tile of mfma_tile.h, the one ital_gram_rows runs on; the
+// Cholesky and the solves are dense.hip's own entry points.  Every sum has a fixed order and no kernel lets one matrix see
+// another: a candidate gets the same bits alone or in any batch.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "ital_evidence.h"
 #include "ital_internal.h"
+#include "mfma_tile.h"
 
 namespace ital {
 namespace evidence {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+using namespace ital::tile;
 
-constexpr int T = 128;         // output tile edge of the Gram kernel
-constexpr int KS = 16;         // k-elements per LDS stage
-constexpr int LDT = T + 4;     // padded row stride of a staged tile (doubles)
 constexpr int CH = 1024;       // columns of a factor row staged per step of the inverse-diagonal kernel
 constexpr int64_t GRID_TARGET_BLOCKS = 512;   // workgroups the Gram grid aims at: 256 CUs x 2
-
-typedef double StageLds[2][2][KS][LDT];   // [buffer][A / B][k][row]
-
-// Lower-triangular tile pair (ti >= tj) of a linear block index t = ti (ti + 1) / 2 + tj.
-__device__ inline void tri_pair(int64_t t, int& ti, int& tj) {
-    int r = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((int64_t)(r + 1) * (r + 2) / 2 <= t) r++;
-    while ((int64_t)r * (r + 1) / 2 > t) r--;
-    ti = r;
-    tj = (int)(t - (int64_t)r * (r + 1) / 2);
-}
-
-// Staging role of a thread: k-pair sk, sk + 1 of the tile rows srow + 8 u, u = 0..3.
-__device__ inline void stage_role(int& sk, int& srow) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    sk = 2 * ((lane & 3) + 4 * (lane >> 5));
-    srow = 32 * wave + ((lane >> 2) & 7);
-}
-
-// acc[p][q] += sum_k A_r[k] B_c[k] over k < K (a multiple of KS) for the 128 x 128 tile of a workgroup of 256 threads: wave
-// (wy, wx) owns rows 64 wy + 16 p + (kg + 4 reg) of A and columns 64 wx + 16 q + col of B (D layout of the f64 MFMA).
-// pa[u] / pb[u]: this thread's staged rows srow + 8 u of A / B, already offset by sk.  Register + LDS double buffer, one
-// barrier per stage; ends with a barrier.
-__device__ inline void tile_nt(const double* const pa[4], const double* const pb[4], int K, StageLds& lds, d4 acc[4][4]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, kg = lane >> 4;
-    const int wy = wave >> 1, wx = wave & 1;
-    int sk, srow;
-    stage_role(sk, srow);
-    double2 ra[4], rb[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            ra[u].x = pa[u][k0];
-            ra[u].y = pa[u][k0 + 1];
-            rb[u].x = pb[u][k0];
-            rb[u].y = pb[u][k0 + 1];
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            lds[buf][0][sk][srow + 8 * u] = ra[u].x;
-            lds[buf][0][sk + 1][srow + 8 * u] = ra[u].y;
-            lds[buf][1][sk][srow + 8 * u] = rb[u].x;
-            lds[buf][1][sk + 1][srow + 8 * u] = rb[u].y;
-        }
-    };
-    fetch(0);
-    stage(0);
-    __syncthreads();
-    const int nstep = K / KS;
-    for (int s_ = 0; s_ < nstep; s_++) {
-        const int buf = s_ & 1;
-        if (s_ + 1 < nstep) fetch((s_ + 1) * KS);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) av[p] = lds[buf][0][4 * kg + j][64 * wy + 16 * p + col];
-#pragma unroll
-            for (int q = 0; q < 4; q++) bv[q] = lds[buf][1][4 * kg + j][64 * wx + 16 * q + col];
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[p], bv[q], acc[p][q], 0, 0, 0);
-        }
-        if (s_ + 1 < nstep) stage(buf ^ 1);
-        __syncthreads();
-    }
-}
 
 // ----------------------------------------------------------------------------------------------------------- Gram grid
 struct GridArgs {
@@ -124,15 +51,12 @@ __global__ __launch_bounds__(256, 2) void gram_grid_kernel(GridArgs a) {
         pb[u] = a.XT + min(j0 + srow + 8 * u, m - 1) * a.ldx + sk;
     }
     d4 acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc[p][q] = (d4){0, 0, 0, 0};
+    zero_acc(acc);
     tile_nt(pa, pb, a.ldx, lds, acc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, kg = lane >> 4;
     const int64_t iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
-    // D = |x_i|^2 + |x_j|^2 - 2 x_i . x_j in place (the expansion of ital_gram_rows; not clamped)
+    // D = |x_i|^2 + |x_j|^2 - 2 x_i . x_j in place (the expansion of ital_gram_rows)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const double bnj = a.xn[min(jw + 16 * q + col, m - 1)];
@@ -141,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void gram_grid_kernel(GridArgs a) {
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
                 const double ani = a.xn[min(iw + 16 * p + kg + 4 * reg, m - 1)];
-                acc[p][q][reg] = ani + bnj - 2 * acc[p][q][reg];
+                acc[p][q][reg] = rbf_sqdist(ani, bnj, acc[p][q][reg]);
             }
     }
     for (int g = blockIdx.y; g < a.G; g += gridDim.y) {

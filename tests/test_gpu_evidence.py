@@ -161,6 +161,35 @@ def test_gram_grid_equals_the_host_kernel_matrix(dev, m, d, G):
         assert np.all(got[~low] == GUARD) and np.all(Kh[g, :, m:] == GUARD)      # the lower triangle and nothing else
 
 
+@pytest.mark.parametrize("d", [5, 20, 40])            # ldx 16, 32, 48: one k-stage; both LDS buffers; an odd count of stages
+@pytest.mark.parametrize("m", [1, 128, 129, 257])     # one tile pair; the exact edge; three pairs, ragged; six pairs
+def test_gram_grid_of_one_candidate_has_the_bits_of_gram_rows(dev, m, d):
+    """ital_gram_grid at G = 1 and ital_gram_rows over rows 0 .. m-1 (identity index) run the same tile (csrc/mfma_tile.h) and
+    the same distance expression: the same bits in the lower triangle, and neither writes anything else."""
+    L, lib = _lib()
+    ls, var, noise = 0.7, 1.3, 1e-3
+    X = np.random.default_rng(77).random((m, d))
+    XT, XTn, ldx = _upload(X, dev)
+    ld = m + 3
+    grid = torch.full((1, m, ld), GUARD, dtype=torch.float64, device=dev)
+    L.check(lib.ital_gram_grid(XT.data_ptr(), XTn.data_ptr(), m, ldx, _params([(ls, var, noise)], dev).data_ptr(), 1,
+                               grid.data_ptr(), ld, _stream()))
+    rows = torch.full((m, ld), GUARD, dtype=torch.float64, device=dev)
+    idx = torch.arange(m, dtype=torch.int64, device=dev)
+    ip, kp, ldp = (torch.tensor([v], dtype=torch.int64, device=dev) for v in (idx.data_ptr(), rows.data_ptr(), ld))
+    npt = torch.tensor([m], dtype=torch.int32, device=dev)
+    L.check(lib.ital_gram_rows(XT.data_ptr(), XTn.data_ptr(), ldx, ip.data_ptr(), npt.data_ptr(), kp.data_ptr(), ldp.data_ptr(),
+                               1, m, var, ls, noise, _stream()))
+    a, b = grid.cpu().numpy()[0], rows.cpu().numpy()
+    low = np.tril(np.ones((m, m), dtype=bool))
+    diff = np.abs(a[:, :m][low] - b[:, :m][low])
+    print("EVID grid vs rows m %d d %d: largest difference %.3g in %d of %d" % (m, d, diff.max(), int((diff > 0).sum()), diff.size))
+    assert not np.any(a[:, :m][low] == GUARD)
+    assert np.array_equal(a[:, :m][low], b[:, :m][low])
+    for got in (a, b):
+        assert np.all(got[:, :m][~low] == GUARD) and np.all(got[:, m:] == GUARD)
+
+
 @pytest.mark.parametrize("m,d,G", SHAPES)
 def test_inverse_diagonals_of_a_batch_of_factors(dev, m, d, G):
     L, lib = _lib()
