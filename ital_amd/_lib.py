@@ -1,5 +1,5 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
-include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h and include/ital_evidence.h).
+include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h and include/ital_ingest.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -249,6 +249,15 @@ EVIDENCE_SIGNATURES = {
 }
 
 
+#: element types of ital_ingest_rows (include/ital_ingest.h)
+INGEST_F64, INGEST_F32, INGEST_F16, INGEST_BF16 = 0, 1, 2, 3
+
+#: feature rows in the caller's type and stride -> padded FP64 rows and norms, declared in include/ital_ingest.h
+INGEST_SIGNATURES = {
+    "ital_ingest_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -269,7 +278,7 @@ def load(path=LIB_PATH):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
-            list(EVIDENCE_SIGNATURES.items()):
+            list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,188 @@
+"""Feature rows that live on the device and are shared: `DeviceData`.
+
+Every kernel reads the data matrix as FP64 rows padded to a multiple of 16 columns, with their squared norms next to them
+(`GaussianProcess.Xd`, `.xnorm`).  A learner built from a numpy array makes its own pair; a `DeviceData` is that pair as an
+object of its own, so that
+
+  - it can be built from whatever the caller has -- numpy or torch, host or device, f16 / bf16 / f32 / f64, row-strided --
+    without a float64 copy on the host and without an n x d FP64 staging tensor on the device (ital_ingest_rows converts,
+    pads and norms; host data travels in its own type, in pieces of at most `chunk_bytes`);
+  - several learners over one database view the same rows (`GaussianProcess(data=store)` uploads nothing);
+  - it grows in place (`append`), and each learner catches up when it chooses to (`sync_data`).
+
+One host thread drives a store and its learners; everything runs on the current torch stream of the store's device.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+
+def _pad16(v):
+    return (int(v) + 15) // 16 * 16
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+#: torch dtype -> element type of ital_ingest_rows (every other real dtype goes through float64)
+DTYPE_CODES = {torch.float64: _lib.INGEST_F64, torch.float32: _lib.INGEST_F32, torch.float16: _lib.INGEST_F16,
+               torch.bfloat16: _lib.INGEST_BF16}
+_NUMPY_CODES = {np.dtype(np.float64): _lib.INGEST_F64, np.dtype(np.float32): _lib.INGEST_F32,
+                np.dtype(np.float16): _lib.INGEST_F16}
+
+
+def dtype_code(dtype):
+    """Element type of ital_ingest_rows for a torch or numpy dtype; None for one that has to be converted first."""
+    if isinstance(dtype, torch.dtype):
+        return DTYPE_CODES.get(dtype)
+    try:
+        return _NUMPY_CODES.get(np.dtype(dtype))
+    except TypeError:
+        return None
+
+
+def as_rows(data):
+    """`data` (numpy array, torch tensor or anything numpy converts) as a 2-D torch tensor of one of the four element types
+    whose inner stride is 1 and whose row stride is at least its width -- on the side it came from, sharing its memory where
+    it already has that form.  ValueError for anything but two dimensions, TypeError for a complex dtype."""
+    if isinstance(data, torch.Tensor):
+        t = data.detach()
+        if t.is_complex():
+            raise TypeError("complex feature rows")
+        if t.ndim != 2:
+            raise ValueError("data must be an n-by-d array")
+        if t.dtype not in DTYPE_CODES:
+            t = t.to(torch.float64)
+    else:
+        a = np.asarray(data)
+        if np.iscomplexobj(a):
+            raise TypeError("complex feature rows")
+        if a.ndim != 2:
+            raise ValueError("data must be an n-by-d array")
+        if a.dtype not in _NUMPY_CODES:
+            a = a.astype(np.float64)
+        item = a.dtype.itemsize
+        if a.shape[1] and (a.strides[1] != item or a.strides[0] % item or a.strides[0] < a.shape[1] * item):
+            a = np.ascontiguousarray(a)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")          # a read-only array: it is only read
+            t = torch.from_numpy(a)
+    if t.shape[1] and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        t = t.contiguous()
+    return t
+
+
+def ingest(t, X, xnorm):
+    """Rows of the DEVICE tensor `t` (as as_rows() leaves it) -> X[i, :] (padded FP64) and xnorm[i], i < len(t), on the
+    current stream.  X: [>= len(t), ldx] float64, contiguous; xnorm: [>= len(t)] float64."""
+    k, d = t.shape
+    if k == 0:
+        return
+    ld = t.stride(0) if k > 1 else d
+    check(_lib.lib().ital_ingest_rows(t.data_ptr(), DTYPE_CODES[t.dtype], k, d, ld, X.data_ptr(), X.shape[1], xnorm.data_ptr(),
+                                      _stream()))
+
+
+class DeviceData(object):
+    """n x d feature rows on `device` as padded FP64 rows `X` [n, ldx] and squared norms `xnorm` [n].
+
+    - data: 2-D numpy array or torch tensor, on the host or on a device; f16 / f32 / f64 (bf16 for tensors) travel and are
+      converted in their own type, any other real dtype goes through float64.  A row-strided view (`T[:, 3:131]`) is read as
+      it is.  The source is never aliased: afterwards the caller may free or overwrite it.
+    - capacity: rows to make room for (at least n); `append` within it writes in place.
+    - chunk_bytes: host data is uploaded in pieces of at most this size, each converted behind its upload.
+    """
+
+    def __init__(self, data, *, device=None, capacity=None, chunk_bytes=256 << 20):
+        if not torch.cuda.is_available():
+            raise RuntimeError("ital_amd.DeviceData needs a HIP device (no CPU fallback)")
+        t = as_rows(data)
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self.chunk_bytes = int(chunk_bytes)
+        self.n = 0
+        self.d = int(t.shape[1])
+        if self.d < 1:
+            raise ValueError("data must have at least one column")
+        self.ldx = _pad16(self.d)
+        self._alloc(max(int(t.shape[0]), int(capacity or 0), 1))
+        self._write(t)
+
+    # ------------------------------------------------------------------ storage
+    def _alloc(self, capacity):
+        with torch.cuda.device(self.device):
+            X = torch.empty((capacity, self.ldx), dtype=torch.float64, device=self.device)
+            xnorm = torch.empty(capacity, dtype=torch.float64, device=self.device)
+            if self.n:
+                # the tensors left behind are not freed here: a learner that still views them keeps them, and its prefix
+                X[: self.n] = self._X[: self.n]
+                xnorm[: self.n] = self._xnorm[: self.n]
+        self._X, self._xnorm, self.capacity = X, xnorm, int(capacity)
+
+    def _write(self, t):
+        """Rows n .. n + len(t) - 1 <- t (there is room), then n grows."""
+        k = int(t.shape[0])
+        if k == 0:
+            return
+        with torch.cuda.device(self.device):
+            X, xnorm = self._X[self.n:], self._xnorm[self.n:]
+            if t.is_cuda:
+                if t.device != self.device:
+                    t = t.to(self.device)
+                ingest(t, X, xnorm)
+            else:
+                step = max(1, self.chunk_bytes // (self.d * t.element_size()))
+                for r0 in range(0, k, step):
+                    piece = t[r0:r0 + step].contiguous().to(self.device)
+                    ingest(piece, X[r0:], xnorm[r0:])
+        self.n += k
+
+    # ------------------------------------------------------------------ what a learner and its caller read
+    @property
+    def X(self):
+        """[n, ldx] view of the rows in use."""
+        return self._X[: self.n]
+
+    @property
+    def xnorm(self):
+        """[n] view of their squared norms."""
+        return self._xnorm[: self.n]
+
+    @property
+    def shape(self):
+        return (self.n, self.d)
+
+    ndim = 2
+
+    def __len__(self):
+        return self.n
+
+    def rows(self, idx=None):
+        """The rows (all, or those of the index list `idx`) as a float64 numpy array: downloaded on demand, not kept."""
+        if idx is None:
+            return self._X[: self.n, : self.d].cpu().numpy()
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < -self.n or idx.max() >= self.n):
+            raise IndexError("row index outside the %d rows" % self.n)
+        sel = torch.from_numpy(idx % max(self.n, 1)).to(self.device)
+        return self._X[: self.n].index_select(0, sel)[:, : self.d].cpu().numpy()
+
+    def append(self, rows):
+        """Adds rows (the input kinds of the constructor) as rows n .. n + k - 1 and returns k.  ValueError, with nothing
+        changed, for another number of columns.  Within the capacity the rows are written in place -- rows >= n are read by
+        nobody: every learner reads up to its own row count; beyond it the store moves to max(2 * capacity, n + k) rows by a
+        device-to-device copy, and learners that still view the old tensors go on with those."""
+        t = as_rows(rows) if not (isinstance(rows, (list, tuple)) and len(rows) == 0) else None
+        if t is None or t.shape[0] == 0:
+            return 0
+        if t.shape[1] != self.d:
+            raise ValueError("rows must be a k-by-%d array" % self.d)
+        k = int(t.shape[0])
+        if self.n + k > self.capacity:
+            self._alloc(max(2 * self.capacity, self.n + k))
+        self._write(t)
+        return k

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib, sharding
 from ._lib import check
+from .device_data import DeviceData
 
 
 def _pad16(v):
@@ -55,7 +56,8 @@ class GaussianProcess(object):
     """GP on a row shard of `data` (rows [row0, row1) on this rank).
 
     # Arguments (as reference ital/gp.py:103-120, plus keyword-only placement):
-    - data: n-by-d array of all samples.
+    - data: n-by-d array of all samples; or a `DeviceData` (rows that are on the device already, shared with every other
+      learner built on it: nothing is uploaded), or a torch tensor (wrapped in a DeviceData of this model's own).
     - length_scale, var, noise: kernel hyper-parameters.
     - device: torch device of this rank.
     - rank / world / group: row sharding over `world` processes (torch.distributed group for the exchange).
@@ -74,7 +76,17 @@ class GaussianProcess(object):
         # one-rank process group (lets a single-GPU box drive the RCCL code path end to end)
         self.collective = self.world > 1 or (group is not None and os.environ.get("ITAL_FORCE_COLLECTIVES") == "1")
         local = None
-        if isinstance(data, sharding.ShardedRows):
+        if isinstance(data, torch.Tensor):
+            if self.world > 1:
+                raise NotImplementedError("a tensor is kept as a DeviceData, which is not sharded: pass ShardedRows to several ranks")
+            data = DeviceData(data, device=self.device)
+        self.store = data if isinstance(data, DeviceData) else None
+        if self.store is not None:
+            if self.world > 1:
+                raise NotImplementedError("a DeviceData is not sharded: pass ShardedRows to several ranks")
+            if self.store.device != self.device:
+                raise ValueError("the DeviceData lives on %s, this model on %s" % (self.store.device, self.device))
+        elif isinstance(data, sharding.ShardedRows):
             local = data
         else:
             data = np.asarray(data, dtype=np.float64)
@@ -92,15 +104,19 @@ class GaussianProcess(object):
         self.length_scale_sq = length_scale * length_scale
         self.var = var
         self.noise = noise
-        self.X_host = data  # the reference keeps a copy too (gp.py:122)
+        self.X_host = data if self.store is None else None  # the reference keeps a copy too (gp.py:122)
         with torch.cuda.device(self.device):
-            Xp = torch.zeros((max(self.n, 1), self.ldx), dtype=torch.float64, device=self.device)
-            if self.n:
-                rows = local.local if local is not None else data[self.row0:self.row1]
-                Xp[: self.n, : self.d] = torch.from_numpy(np.ascontiguousarray(rows)).to(self.device)
-            self.Xd = Xp
-            self.xnorm = torch.empty(max(self.n, 1), dtype=torch.float64, device=self.device)
-            check(self._lib.ital_row_norms(_ptr(self.Xd), self.n, self.ldx, _ptr(self.xnorm), _stream()))
+            if self.store is not None:
+                # views of the shared rows up to THIS model's row count: no upload, no norms launch
+                self.Xd, self.xnorm = self.store.X, self.store.xnorm
+            else:
+                Xp = torch.zeros((max(self.n, 1), self.ldx), dtype=torch.float64, device=self.device)
+                if self.n:
+                    rows = local.local if local is not None else data[self.row0:self.row1]
+                    Xp[: self.n, : self.d] = torch.from_numpy(np.ascontiguousarray(rows)).to(self.device)
+                self.Xd = Xp
+                self.xnorm = torch.empty(max(self.n, 1), dtype=torch.float64, device=self.device)
+                check(self._lib.ital_row_norms(_ptr(self.Xd), self.n, self.ldx, _ptr(self.xnorm), _stream()))
             self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._gather_bufs = {}
             if capacity is None:
@@ -131,7 +147,7 @@ class GaussianProcess(object):
 
     @property
     def X(self):
-        return self.X_host
+        return self.X_host if self.store is None else self.store.rows()[: self.n_total]
 
     @property
     def K_all(self):
@@ -397,7 +413,11 @@ class GaussianProcess(object):
         entries of `ind` move up by len(rows).  The reference has no such call: its dense K_all (gp.py:128) is built once.
 
         An empty array is a no-op; ValueError (nothing changed) for another number of columns; NotImplementedError on
-        several ranks: row sharding cannot grow yet."""
+        several ranks: row sharding cannot grow yet.  On a DeviceData: store.append(rows), then sync_data()."""
+        if self.store is not None:
+            self.store.append(rows)
+            self.sync_data()
+            return self
         rows = np.asarray(rows, dtype=np.float64)
         if rows.size == 0:
             return self
@@ -430,6 +450,60 @@ class GaussianProcess(object):
             self._whiten_rows(n_old, k)
             self._replicate_mean()
         return self
+
+    def sync_data(self):
+        """Catches up with the growth of the DeviceData this model was built on: what extend() does, minus the growth of Xd
+        and xnorm -- new views up to store.n; V (new leading dimension), mu and s2 grow by device-to-device copies; the new
+        range alone is whitened against the labelled set (ital_whiten_rows); the means are replicated; query rows move up in
+        `ind`.  Returns the number of rows gained; 0 changes nothing.  Until it is called the model goes on on its own n rows,
+        also across a reallocation of the store (its views keep the old tensors alive).  ValueError without a DeviceData."""
+        if self.store is None:
+            raise ValueError("this model owns its rows: build it on a DeviceData to share and grow them")
+        n_old, n_new, m, dev = self.n, self.store.n, self.m, self.device
+        k = n_new - n_old
+        if k == 0:
+            return 0
+        ldv = _pad16(n_new)
+        with torch.cuda.device(dev):
+            mu = torch.empty(n_new, dtype=torch.float64, device=dev)
+            s2 = torch.empty(n_new, dtype=torch.float64, device=dev)
+            V = torch.zeros((self.cap, ldv), dtype=torch.float64, device=dev)
+            mu[:n_old], s2[:n_old] = self.mu[:n_old], self.s2[:n_old]
+            if m and n_old:
+                V[:m, :n_old] = self.V[:m, :n_old]
+            self.Xd, self.xnorm, self.mu, self.s2, self.V = self.store.X, self.store.xnorm, mu, s2, V
+            self.n, self.ldv = n_new, ldv
+            self.ind = [i + k if i >= self.n_total else i for i in self.ind]
+            self.n_total += k
+            self.row1 = self.row0 + n_new
+            self._append_desc = None          # it holds X, xnorm, n and ldv
+            self._gather_bufs = {}
+            self._whiten_rows(n_old, k)       # writes the new rows' xnorm again: the bits the store already holds
+            self._replicate_mean()
+        return k
+
+    def clone(self):
+        """A second model on the same DeviceData in this model's state: same row count (also when the store has grown since),
+        same hyper-parameters; V[:m], L, alpha, XT, XTn, mu, s2 and the status word are copied device to device, the labelled
+        set and `appends` on the host.  Work buffers are not carried over.  ValueError for a model that owns its rows."""
+        if self.store is None:
+            raise ValueError("clone() shares the rows between the two models: build the model on a DeviceData "
+                             "(ital_amd.DeviceData(data)) instead of a numpy array")
+        g = object.__new__(GaussianProcess)
+        g.__dict__.update(self.__dict__)
+        for name in ("_append_desc", "_ybuf", "_remove_work", "_topk_work", "host_clock"):
+            g.__dict__.pop(name, None)
+        g.ind, g.appends = list(self.ind), list(self.appends)
+        g.y = None if self.y is None else self.y.copy()
+        with torch.cuda.device(self.device):
+            g.V = torch.zeros_like(self.V)
+            if self.m:
+                g.V[: self.m] = self.V[: self.m]
+            g.L, g.alpha, g.XT, g.XTn = self.L.clone(), self.alpha.clone(), self.XT.clone(), self.XTn.clone()
+            g.mu, g.s2, g.status = self.mu.clone(), self.s2.clone(), self.status.clone()
+            g._gather_bufs = {}
+            g._replicate_mean()
+        return g
 
     def set_params(self, length_scale=None, var=None, noise=None):
         """Other kernel hyper-parameters for a live model (None: as it is), e.g. what ital_amd.tune found: the factor and alpha
@@ -681,16 +755,24 @@ class GaussianProcess(object):
 
     def predict(self, X, cov_mode=None):
         """Predictive mean (and variance / full covariance) for external samples (reference gp.py:264-292).  Every rank
-        computes it for all of X (the labelled-set state is replicated): no collective."""
+        computes it for all of X (the labelled-set state is replicated): no collective.  X: an array, or a torch tensor
+        (f16 / bf16 / f32 / f64, host or device) that ital_ingest_rows converts on the device."""
         if self.m == 0:
             raise RuntimeError("the GP has not been fitted")
         if cov_mode not in (None, "diag", "full"):
             raise ValueError("cov_mode must be None, 'diag' or 'full'")
-        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-        nt = X.shape[0]
         dev = self.device
-        Xt = torch.zeros((nt, self.ldx), dtype=torch.float64, device=dev)
-        Xt[:, : self.d] = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
+        if isinstance(X, torch.Tensor):
+            # f16 / bf16 / f32 / f64, host or device: converted and padded on the device (the same bits as the float64 array)
+            Xt = DeviceData(X if X.ndim != 1 else X[None], device=dev)
+            if Xt.d != self.d:
+                raise ValueError("X must have %d columns" % self.d)
+            nt, Xt = Xt.n, Xt.X
+        else:
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            nt = X.shape[0]
+            Xt = torch.zeros((nt, self.ldx), dtype=torch.float64, device=dev)
+            Xt[:, : self.d] = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
         ldvt = _pad16(nt)
         mean = torch.empty(nt, dtype=torch.float64, device=dev)
         pvar = torch.empty(nt, dtype=torch.float64, device=dev)

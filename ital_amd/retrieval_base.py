@@ -11,7 +11,10 @@ below them (GP state, candidate bookkeeping, the device path) is this package's 
 """
 import numpy as np
 
+import copy
+
 from . import tune
+from .device_data import DeviceData
 from .gp import GaussianProcess
 
 
@@ -131,7 +134,14 @@ class ActiveRetrievalBase(object):
         self.fit(data, queries)
 
     def fit(self, data, queries=[]):
-        """reference retrieval_base.py:34-45"""
+        """reference retrieval_base.py:34-45.  `data`: an array; or a DeviceData (rows on the device, shared by every learner
+        built on it), or a torch tensor, which becomes a DeviceData of this learner's own -- `self.data` is then that store."""
+        if data is not None and not isinstance(data, DeviceData):
+            import torch
+            if isinstance(data, torch.Tensor):
+                if self.world > 1:
+                    raise NotImplementedError("a tensor is kept as a DeviceData, which is not sharded: pass ShardedRows to several ranks")
+                data = DeviceData(data, device=self.device)
         self.data = data
         self.queries = queries
         if self.data is not None:
@@ -140,6 +150,12 @@ class ActiveRetrievalBase(object):
             self.reset()
         else:
             self.gp = None
+
+    def _num_samples(self):
+        """len(self.data) -- except on a DeviceData that has grown since this learner last called sync_data(): the learner
+        goes on on the rows it knows."""
+        gp = self.__dict__.get("gp")
+        return gp.n_total if gp is not None and gp.store is not None else len(self.data)
 
     def reset(self):
         """reference retrieval_base.py:48-61"""
@@ -150,7 +166,7 @@ class ActiveRetrievalBase(object):
         self._last_batch = None
         self.gp.reset()
         if len(self.queries) > 0:
-            n = len(self.data)
+            n = self._num_samples()
             self.gp.update_points(self.queries, [1] * len(self.queries), ind=list(range(n, n + len(self.queries))))
             self._fitted = True
         else:
@@ -167,7 +183,7 @@ class ActiveRetrievalBase(object):
         batches, so the means agree to ~1e-15, not bit for bit (a pick at an exact numerical tie may differ)."""
         from . import mvn_stream
         gp = self.gp
-        return dict(version=1, n=len(self.data), hyper=(float(self.length_scale), float(self.var), float(self.noise)),
+        return dict(version=1, n=self._num_samples(), hyper=(float(self.length_scale), float(self.var), float(self.noise)),
                     ind=[int(i) for i in gp.ind], y=(gp.y.copy() if gp.y is not None else np.zeros(0)),
                     appends=list(gp.appends), relevant_ids=sorted(self.relevant_ids),
                     irrelevant_ids=sorted(self.irrelevant_ids), unnameable_ids=sorted(self.unnameable_ids),
@@ -181,7 +197,7 @@ class ActiveRetrievalBase(object):
         process-wide positions of the two random streams (mvndst's, numpy's global generator).  Collective on several ranks,
         like update()."""
         from . import mvn_stream
-        if sd.get("version") != 1 or sd["n"] != len(self.data):
+        if sd.get("version") != 1 or sd["n"] != self._num_samples():
             raise ValueError("state_dict of another data set / version")
         if tuple(sd["hyper"]) != (float(self.length_scale), float(self.var), float(self.noise)):
             raise ValueError("state_dict was saved with other hyper-parameters: %r" % (sd["hyper"],))
@@ -219,7 +235,7 @@ class ActiveRetrievalBase(object):
         ties by descending index as the reversal of a stable ascending sort gives); the complete ranking (k = None) is
         N-sized by definition and sorts the downloaded means on the host."""
         from ._lib import ITAL_TOPK_MAX
-        if k is not None and self._fitted and 1 <= int(k) <= min(ITAL_TOPK_MAX, len(self.data)):
+        if k is not None and self._fitted and 1 <= int(k) <= min(ITAL_TOPK_MAX, self._num_samples()):
             return self.gp.topk_mean(int(k))
         ind = np.argsort(self.rel_mean, kind="stable")[::-1]
         return ind[:k] if k is not None else ind
@@ -263,9 +279,9 @@ class ActiveRetrievalBase(object):
             return u[0]
         seen = self.relevant_ids | self.irrelevant_ids | self.unnameable_ids
         if not seen:
-            arr = np.arange(len(self.data), dtype=np.int64)
+            arr = np.arange(self._num_samples(), dtype=np.int64)
         else:
-            mask = np.ones(len(self.data), dtype=bool)
+            mask = np.ones(self._num_samples(), dtype=bool)
             mask[np.fromiter(seen, dtype=np.int64, count=len(seen))] = False
             arr = np.flatnonzero(mask)
         lst = UnseenList(arr)
@@ -340,7 +356,13 @@ class ActiveRetrievalBase(object):
         """Appends samples to a live session (GaussianProcess.extend): the new ones get the ids len(data) .. and are unseen;
         feedback, `rounds` and both random streams stay as they are.  The reference would need a new learner (and a new
         dense K_all, gp.py:128).  An empty array is a no-op; ValueError (nothing changed) for another number of columns;
-        NotImplementedError on several ranks: row sharding cannot grow yet."""
+        NotImplementedError on several ranks: row sharding cannot grow yet.  A learner on a DeviceData: store.append(rows)
+        -- any input kind the store takes -- followed by sync_data(); other learners on the store catch up when they call
+        sync_data() themselves."""
+        if isinstance(self.data, DeviceData):
+            if self.data.append(rows):
+                self.sync_data()
+            return self
         rows = np.asarray(rows, dtype=np.float64)
         if rows.size == 0:
             return self
@@ -352,6 +374,47 @@ class ActiveRetrievalBase(object):
         self.data = self.gp.X_host
         self._start_afresh()
         return self
+
+    def sync_data(self):
+        """A learner on a DeviceData takes in the rows the store has gained since its construction or its last sync_data()
+        (GaussianProcess.sync_data: only the new range is whitened): they get the ids that follow and are unseen; feedback,
+        `rounds` and both random streams stay as they are.  Returns the number of rows gained (0: nothing is touched).
+        ValueError for a learner that owns its rows."""
+        if not isinstance(self.data, DeviceData):
+            raise ValueError("this learner owns its rows: build it on a DeviceData to share and grow them")
+        k = self.gp.sync_data()
+        if k:
+            self._start_afresh()
+        return k
+
+    #: attributes that hold buffers or caches of one learner's last fetch: a clone starts without them
+    _FETCH_STATE = ("_unseen", "_last_batch", "_fetch_bufs", "_round_bufs", "_block_bufs", "_gram_bufs", "_err_bufs",
+                    "_ce_subset", "_transport", "last", "last_scores", "last_round", "profile", "pair_counter", "host_clock")
+
+    def clone(self):
+        """A second learner of the same class and options on the same DeviceData, in this learner's state: the GP's device
+        state is copied device to device (GaussianProcess.clone), the labelled set, the three id sets and `rounds` on the
+        host; the buffers of the last fetch are not carried over -- the clone builds its own on its next fetch.  The two
+        branches then take different feedback without a second copy of the rows: a what-if, or a session handed on.  The two
+        random streams are process-wide and are not touched.  ValueError for a learner built from a numpy array."""
+        if not isinstance(self.data, DeviceData):
+            raise ValueError("clone() shares the rows between the two learners: build the learner on a DeviceData "
+                             "(ital_amd.DeviceData(data)) instead of a numpy array")
+        new = object.__new__(type(self))
+        for name, value in self.__dict__.items():
+            if name in self._FETCH_STATE:
+                value = None
+            elif isinstance(value, (list, dict)) and not isinstance(value, IdSet):
+                value = copy.copy(value)
+            new.__dict__[name] = value
+        if "_pinned" in new.__dict__:
+            new._pinned = {}
+        if "event_pool" in new.__dict__:
+            new.event_pool = []
+        new.gp = self.gp.clone()
+        new.relevant_ids, new.irrelevant_ids, new.unnameable_ids = set(self.relevant_ids), set(self.irrelevant_ids), \
+            set(self.unnameable_ids)
+        return new
 
     def set_params(self, length_scale=None, var=None, noise=None):
         """Other kernel hyper-parameters for a live session (None: as it is), e.g. the result of ital_amd.tune
