@@ -7,7 +7,8 @@ import collections
 import torch
 
 from . import mvn_stream, sharding
-from ._lib import ITAL_JUMP_BITS, ItalBatch, check, lib as _lib
+from ._lib import ITAL_JUMP_BITS, ItalBatch, check, lib as _lib, rows_fn
+from .device_data import DTYPE_CODES
 
 LABEL_MODES = {"mean": 0, "optimistic": 1, "pessimistic": 2}
 FUSED_LAUNCH_MAX = 1 << 18   # one rank, up to this many candidates: ital_select_fused (one workgroup) as the separate selection launch
@@ -66,11 +67,12 @@ def select_step(gp, b, scored, model, slot, st, *, argmin=0, fused=False, local=
     s, m = scored, model
     head = (_ptr(s.scores), _ptr(s.cand), _ptr(s.alive), s.n, s.pos_offset, _ptr(s.gpos), s.row_offset, gp.rank, argmin,
             _ptr(m.mu), _ptr(m.s2), _ptr(m.X), _ptr(m.xnorm), m.ldx, _ptr(m.V), m.ldv, m.m, m.cap, _ptr(b["C"]), m.ldv, slot)
+    xtype = DTYPE_CODES[m.X.dtype]       # the model's rows: FP64, or views of a compact store (the record is FP64 either way)
     if fused:
-        check(lib.ital_select_fused(*head, slot, b["batch"], _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]), st))
+        check(rows_fn("ital_select_fused", xtype)(*head, slot, b["batch"], _ptr(gp.status), _ptr(b["rec"]), _ptr(b["ret"]), st))
         return None
     if local:
-        check(lib.ital_select_local(*head, b["kmax"], _ptr(gp.status), _ptr(b["work"]), _ptr(b["rec"]), st))
+        check(rows_fn("ital_select_local", xtype)(*head, b["kmax"], _ptr(gp.status), _ptr(b["work"]), _ptr(b["rec"]), st))
     recs = b["rec"]
     if gp.collective:
         ev0 = mark() if mark else None
@@ -88,9 +90,9 @@ def member_column(learner, model, b, slot, st, member=None):
     `member`: its (feature row, squared norm, whitened column) when they are not the batch state's own."""
     x, xn, v = member if member is not None else (b["XB"][slot], b["XBn"][slot:], b["VB"][slot])
     m = model
-    check(_lib().ital_cross_cov_cols(_ptr(m.X), _ptr(m.xnorm), m.n, m.ldx, _ptr(x), _ptr(xn), 1, _ptr(v), m.cap, _ptr(m.V),
-                                     m.ldv, m.m, float(learner.var), float(learner.length_scale), _ptr(b["C"][slot]), m.ldv,
-                                     st))
+    check(rows_fn("ital_cross_cov_cols", DTYPE_CODES[m.X.dtype])(
+        _ptr(m.X), _ptr(m.xnorm), m.n, m.ldx, _ptr(x), _ptr(xn), 1, _ptr(v), m.cap, _ptr(m.V), m.ldv, m.m, float(learner.var),
+        float(learner.length_scale), _ptr(b["C"][slot]), m.ldv, st))
 
 
 def lattice_tables(b, t, dev):

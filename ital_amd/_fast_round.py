@@ -270,7 +270,7 @@ class FastRound(object):
 
     def _call(self):
         rb = self.rb
-        rc = _lib.lib().ital_fetch_round(ctypes.byref(self.p.desc), _stream())
+        rc = _lib.rows_fn("ital_fetch_round", self.gp.xtype)(ctypes.byref(self.p.desc), _stream())
         if rc and rb.exchange_exc is not None:      # the host transport's callback failed: its own error, not the C one
             exc, rb.exchange_exc = rb.exchange_exc, None
             raise exc

@@ -84,7 +84,7 @@ class GenericRound(object):
             c = min(16, len(E) - c0)
             Wt = torch.zeros((c, gp.cap), dtype=torch.float64, device=dev)
             Wt[:, : gp.m] = vcols[: gp.m, c0:c0 + c].t()
-            check(self.lib.ital_cross_cov_cols(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(rows[c0:c0 + c]),
+            check(_lib.rows_fn("ital_cross_cov_cols", gp.xtype)(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(rows[c0:c0 + c]),
                                                _ptr(norms[c0:c0 + c]), c, _ptr(Wt), gp.cap, _ptr(gp.V), gp.ldv, gp.m,
                                                float(self.L.var), float(self.L.length_scale), _ptr(C[c0:c0 + c]), gp.ldv,
                                                self.st))

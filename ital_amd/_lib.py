@@ -1,5 +1,6 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
-include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h and include/ital_ingest.h).
+include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_ingest.h and
+include/ital_rows.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -258,6 +259,23 @@ INGEST_SIGNATURES = {
 }
 
 
+def _typed(sig):
+    """The binding of ital_NAME_t from that of ital_NAME: the element type of X goes in front of the stream."""
+    res, args = sig
+    return (res, args[:-1] + [c_int, args[-1]])
+
+
+#: the readers of whole feature rows with the element type of X as an argument (`xtype`: the INGEST_* codes), and the ingest
+#: that keeps the source's type, declared in include/ital_rows.h
+ROWS_SIGNATURES = dict(
+    [(name + "_t", _typed(SIGNATURES[name])) for name in
+     ("ital_rbf_cols", "ital_cross_cov_cols", "ital_whiten_append", "ital_gp_append", "ital_score_step", "ital_fetch_round",
+      "ital_select_local", "ital_select_fused", "ital_gather_block")] +
+    [("ital_whiten_rows_t", _typed(REWHITEN_SIGNATURES["ital_whiten_rows"])),
+     ("ital_ingest_rows_t", (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                     c_void_p]))])
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -278,7 +296,7 @@ def load(path=LIB_PATH):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
-            list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()):
+            list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args
@@ -293,6 +311,15 @@ def lib():
     if _lib is None:
         _lib = load()
     return _lib
+
+
+def rows_fn(name, xtype):
+    """ital_NAME for FP64 rows; for rows of another element type ital_NAME_t, called with ital_NAME's arguments (the type is
+    put in front of the stream)."""
+    if xtype == INGEST_F64:
+        return getattr(lib(), name)
+    fn = getattr(lib(), name + "_t")
+    return lambda *args: fn(*(args[:-1] + (xtype, args[-1])))
 
 
 def check(rc):

@@ -11,7 +11,7 @@ import torch
 from scipy.special import ndtr
 
 from . import mvn_stream, sharding
-from ._lib import check
+from ._lib import check, rows_fn
 from .gp import _pad16, _ptr, _stream
 from .ital import ITAL
 from .retrieval_base import ActiveRetrievalBase
@@ -76,9 +76,9 @@ class VarianceSampling(_RankingLearner):
         w = torch.zeros((1, gp.cap), dtype=torch.float64, device=gp.device)
         w[0, : gp.m] = gp.gather_columns(gp.V[: max(gp.m, 1)], [int(i)])[: gp.m, 0]
         out = torch.empty(gp.ldv, dtype=torch.float64, device=gp.device)
-        check(gp._lib.ital_cross_cov_cols(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(row), _ptr(nrm), 1, _ptr(w), gp.cap,
-                                          _ptr(gp.V), gp.ldv, gp.m, float(self.var), float(self.length_scale), _ptr(out),
-                                          gp.ldv, _stream()))
+        check(rows_fn("ital_cross_cov_cols", gp.xtype)(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, gp.ldx, _ptr(row), _ptr(nrm), 1, _ptr(w),
+                                                       gp.cap, _ptr(gp.V), gp.ldv, gp.m, float(self.var),
+                                                       float(self.length_scale), _ptr(out), gp.ldv, _stream()))
         return gp._full(out)
 
     def fetch_unlabelled(self, k):
@@ -149,6 +149,10 @@ class EMOC(ActiveRetrievalBase):
 
     def _mean_abs_cov(self):
         gp = self.gp
+        if gp.xtype != 0:
+            raise NotImplementedError("EMOC cannot run on a compact store (DeviceData(storage='source'), %s rows): "
+                                      "ital_cov_abs_rowsum reads FP64 rows on both sides; build the store with storage='f64'"
+                                      % gp.Xd.dtype)
         dev = gp.device
         lib = gp._lib
         with torch.cuda.device(dev):

@@ -12,6 +12,8 @@
 #include "device_math.h"
 #include "ital_hip.h"
 #include "ital_internal.h"
+#include "ital_rows.h"
+#include "rows_elem.h"
 
 namespace ital {
 
@@ -221,7 +223,13 @@ extern "C" int ital_chol_append(const double* XT, const double* XTn, int ldx, do
 // update() of the retrieval loop as ONE call (reference ital/gp.py:164-200 + predict_stored, gp.py:203-232): the samples'
 // rows staged out of `rows`, the rank-c Cholesky append (both in one single-workgroup launch) and the whitening sweep.
 extern "C" int ital_gp_append(const ital_append_desc* a, hipStream_t stream) {
+    return ital_gp_append_t(a, ITAL_INGEST_F64, stream);
+}
+
+extern "C" int ital_gp_append_t(const ital_append_desc* a, int xtype, hipStream_t stream) {
     if (!a) return ital_fail(-22, "ital_gp_append: null descriptor");
+    const int trc = ital_rows_check(a->X, xtype, "ital_gp_append: unknown element type of X", "ital_gp_append: X must be aligned to 16 B");
+    if (trc) return trc;
     const int c = a->lb.c, m = a->m;
     if (c < 1 || c > 16) return ital_fail(-22, "ital_gp_append: 1..16 samples per call");
     if (m < 0 || m + c > a->ldl) return ital_fail(-22, "ital_gp_append: factor capacity exceeded");
@@ -232,6 +240,6 @@ extern "C" int ital_gp_append(const ital_append_desc* a, hipStream_t stream) {
     const int rc = ital_check_launch("ital_gp_append(chol)");
     if (rc) return rc;
     const double* L21 = a->L + (int64_t)m * a->ldl;
-    return ital_whiten_append(a->X, a->xnorm, a->n, a->ldx, a->XT + (int64_t)m * a->ldx, a->XTn + m, c, L21, a->ldl, L21 + m,
-                              a->alpha + m, a->V, a->ldv, m, a->var, a->length_scale, a->mu, a->s2, stream);
+    return ital_whiten_append_t(a->X, a->xnorm, a->n, a->ldx, a->XT + (int64_t)m * a->ldx, a->XTn + m, c, L21, a->ldl, L21 + m,
+                                a->alpha + m, a->V, a->ldv, m, a->var, a->length_scale, a->mu, a->s2, xtype, stream);
 }

@@ -15,7 +15,8 @@
 //               of V; s2 -= colsum(V_new^2); mu += V_new^T alpha_new   (GP update, rank-c Cholesky append)
 //   MODE_PREDICT out_mean[i] += ..., used for gp.predict on external points (see predict kernel below)
 //
-// Data layout: X row-major [n][ldx] fp64, ldx = d padded to a multiple of 16 with zeros (rows 128-B aligned);
+// Data layout: X row-major [n][ldx] fp64 -- or, for a store kept in its source precision (include/ital_rows.h), f32 / f16 /
+// bf16 elements that the operand fetch widens exactly --, ldx = d padded to a multiple of 16 with zeros (rows 128-B aligned);
 // V row-major [m_max][ldv] (one contiguous n-vector per labelled point, coalesced across candidates).
 // HBM-bound: algorithmic bytes per row = 8*(d + m) read + 8*c written; the MFMA pipe has ~3x headroom.
 #include <hip/hip_runtime.h>
@@ -24,7 +25,9 @@
 #include "device_math.h"
 #include "ital_hip.h"
 #include "ital_internal.h"
+#include "ital_rows.h"
 #include "qmc_seed.h"
+#include "rows_elem.h"
 
 namespace ital {
 
@@ -49,7 +52,7 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const double* __restrict
 }
 
 struct KcolsArgs {
-    const double* X;      // [n][ldx]
+    const void* X;        // [n][ldx] of the element type the kernel is instantiated for (rows_elem.h)
     const double* xnorm;  // [n]
     int64_t n;
     int ldx;              // padded feature dim, multiple of 16
@@ -79,6 +82,9 @@ enum { MODE_RAW = 0, MODE_WHITEN = 1 };
 #endif
 constexpr int KU = ITAL_KCOLS_KU;   // feature steps per trip of the dot-product loop
 
+// E: element type of X (rows_elem.h).  Only the operand fetch of the data rows depends on it: a lane's four features of a
+// step are one vector load in X's type, widened (exactly) when the MFMA takes them; Xs, W, V and the epilogues are FP64.
+template <class E>
 __device__ __forceinline__ void kcols_body(const KcolsArgs& a) {
     __shared__ double tile[4][16][17];  // per wave: R[j][i] transpose buffer for the whitening epilogue
     const int lane = threadIdx.x & 63;
@@ -90,7 +96,7 @@ __device__ __forceinline__ void kcols_body(const KcolsArgs& a) {
     const int64_t irow = i0 + col;            // data row this lane feeds as B column
     const bool row_ok = irow < a.n;
     const bool sel_ok = col < a.c;            // selected point this lane feeds as A row
-    const double* xrow = a.X + (row_ok ? irow : 0) * a.ldx;
+    const typename E::raw* xrow = static_cast<const typename E::raw*>(a.X) + (row_ok ? irow : 0) * a.ldx;
     const double* srow = a.Xs + (sel_ok ? col : 0) * (int64_t)a.ldx;
 
     d4 acc_dot = {0, 0, 0, 0};
@@ -98,16 +104,15 @@ __device__ __forceinline__ void kcols_body(const KcolsArgs& a) {
     // KU steps of 16 features per trip, all their loads issued before the first MFMA: at the sizes where the kernel is
     // latency bound (a few hundred waves) the operand fetches of a trip overlap instead of queueing behind each other.
     for (int k0 = 0; k0 < a.ldx; k0 += 16 * KU) {
-        double2 b01[KU], b23[KU], a01[KU], a23[KU];
+        Quads<E, KU> b;
+        double2 a01[KU], a23[KU];
 #pragma unroll
         for (int u = 0; u < KU; u++) {
             const int kk = k0 + 16 * u + 4 * kg;
             const bool in = k0 + 16 * u < a.ldx;           // ldx is a multiple of 16
-            b01[u] = b23[u] = a01[u] = a23[u] = double2{0, 0};
-            if (in && row_ok) {
-                b01[u] = *reinterpret_cast<const double2*>(xrow + kk);
-                b23[u] = *reinterpret_cast<const double2*>(xrow + kk + 2);
-            }
+            a01[u] = a23[u] = double2{0, 0};
+            b.zero(u);
+            if (in && row_ok) b.load(u, xrow + kk);
             if (in && sel_ok) {
                 a01[u] = *reinterpret_cast<const double2*>(srow + kk);
                 a23[u] = *reinterpret_cast<const double2*>(srow + kk + 2);
@@ -115,10 +120,10 @@ __device__ __forceinline__ void kcols_body(const KcolsArgs& a) {
         }
 #pragma unroll
         for (int u = 0; u < KU; u++) {
-            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u].x, b01[u].x, acc_dot, 0, 0, 0);
-            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u].y, b01[u].y, acc_dot, 0, 0, 0);
-            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u].x, b23[u].x, acc_dot, 0, 0, 0);
-            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u].y, b23[u].y, acc_dot, 0, 0, 0);
+            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u].x, b.get(u, 0), acc_dot, 0, 0, 0);
+            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u].y, b.get(u, 1), acc_dot, 0, 0, 0);
+            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u].x, b.get(u, 2), acc_dot, 0, 0, 0);
+            acc_dot = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u].y, b.get(u, 3), acc_dot, 0, 0, 0);
         }
     }
     // ---- S = W V over the labelled dimension: A[j][r] = W[j][r], B[r][i] = V[r][i]
@@ -186,7 +191,11 @@ __device__ __forceinline__ void kcols_body(const KcolsArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void kcols_kernel(KcolsArgs a) { kcols_body(a); }
+__global__ __launch_bounds__(256) void kcols_kernel(KcolsArgs a) { kcols_body<IngestF64>(a); }
+
+// The same sweep over rows kept in their source precision (include/ital_rows.h); the FP64 kernel above keeps its name.
+template <class E>
+__global__ __launch_bounds__(256) void kcols_rows_kernel(KcolsArgs a) { kcols_body<E>(a); }
 
 // The covariance column of the member just selected AND the generator states of the next greedy step's candidates in one
 // launch: both depend on nothing but that selection, both are short (10 us each at 9298 rows) -- the first `nk` workgroups
@@ -196,7 +205,16 @@ __global__ __launch_bounds__(256) void kcols_seed_kernel(KcolsArgs a, SeedArgs s
         qmc_seed_body(s, (int64_t)(blockIdx.x - nk) * 256 + threadIdx.x);
         return;
     }
-    kcols_body(a);
+    kcols_body<IngestF64>(a);
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void kcols_rows_seed_kernel(KcolsArgs a, SeedArgs s, unsigned nk) {
+    if (blockIdx.x >= nk) {
+        qmc_seed_body(s, (int64_t)(blockIdx.x - nk) * 256 + threadIdx.x);
+        return;
+    }
+    kcols_body<E>(a);
 }
 
 // gp.predict on external points (reference ital/gp.py:264-292): the test points are whitened against the labelled set
@@ -255,39 +273,63 @@ extern "C" int ital_row_norms(const double* X, int64_t n, int ldx, double* xnorm
     return ital_check_launch("ital_row_norms");
 }
 
-static int launch_kcols(KcolsArgs& a, hipStream_t stream, const char* who) {
+static int launch_kcols(KcolsArgs& a, int xtype, hipStream_t stream, const char* who) {
     if (a.n <= 0) return 0;
     if (a.ldx % 16 != 0) return ital_fail(-22, "kcols: ldx must be a multiple of 16");
     if (a.c < 1 || a.c > 16) return ital_fail(-22, "kcols: c must be in 1..16");
     if (a.m < 0 || (a.m > 0 && (!a.W || !a.V))) return ital_fail(-22, "kcols: W/V missing");
-    int64_t blocks = (a.n + 63) / 64;
-    ITAL_LAUNCH(kcols_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    const dim3 blocks((unsigned)((a.n + 63) / 64));
+    switch (xtype) {
+        case ITAL_INGEST_F64: ITAL_LAUNCH(kcols_kernel, blocks, dim3(256), 0, stream, a); break;
+        case ITAL_INGEST_F32: ITAL_LAUNCH(kcols_rows_kernel<IngestF32>, blocks, dim3(256), 0, stream, a); break;
+        case ITAL_INGEST_F16: ITAL_LAUNCH(kcols_rows_kernel<IngestF16>, blocks, dim3(256), 0, stream, a); break;
+        default: ITAL_LAUNCH(kcols_rows_kernel<IngestBF16>, blocks, dim3(256), 0, stream, a); break;
+    }
     return ital_check_launch(who);
+}
+
+extern "C" int ital_rbf_cols_t(const void* X, const double* xnorm, int64_t n, int ldx, const double* Xs, const double* sn,
+                               int c, double var, double length_scale, double* out, int64_t ldo, int xtype,
+                               hipStream_t stream) {
+    const int rc = ital_rows_check(X, xtype, "ital_rbf_cols: unknown element type of X", "ital_rbf_cols: X must be aligned to 16 B");
+    if (rc) return rc;
+    KcolsArgs a = {};
+    a.X = X; a.xnorm = xnorm; a.n = n; a.ldx = ldx; a.Xs = Xs; a.sn = sn; a.c = c;
+    a.m = 0; a.var = var; a.s = -2.0 * length_scale * length_scale; a.mode = MODE_RAW; a.out = out; a.ldo = ldo;
+    return launch_kcols(a, xtype, stream, "ital_rbf_cols");
 }
 
 extern "C" int ital_rbf_cols(const double* X, const double* xnorm, int64_t n, int ldx, const double* Xs,
                              const double* sn, int c, double var, double length_scale, double* out, int64_t ldo,
                              hipStream_t stream) {
+    return ital_rbf_cols_t(X, xnorm, n, ldx, Xs, sn, c, var, length_scale, out, ldo, ITAL_INGEST_F64, stream);
+}
+
+extern "C" int ital_cross_cov_cols_t(const void* X, const double* xnorm, int64_t n, int ldx, const double* Xs,
+                                     const double* sn, int c, const double* W, int ldw, const double* V, int64_t ldv, int m,
+                                     double var, double length_scale, double* out, int64_t ldo, int xtype,
+                                     hipStream_t stream) {
+    const int rc = ital_rows_check(X, xtype, "ital_cross_cov_cols: unknown element type of X",
+                                   "ital_cross_cov_cols: X must be aligned to 16 B");
+    if (rc) return rc;
     KcolsArgs a = {};
     a.X = X; a.xnorm = xnorm; a.n = n; a.ldx = ldx; a.Xs = Xs; a.sn = sn; a.c = c;
-    a.m = 0; a.var = var; a.s = -2.0 * length_scale * length_scale; a.mode = MODE_RAW; a.out = out; a.ldo = ldo;
-    return launch_kcols(a, stream, "ital_rbf_cols");
+    a.W = W; a.ldw = ldw; a.V = V; a.ldv = ldv; a.m = m;
+    a.var = var; a.s = -2.0 * length_scale * length_scale; a.mode = MODE_RAW; a.out = out; a.ldo = ldo;
+    return launch_kcols(a, xtype, stream, "ital_cross_cov_cols");
 }
 
 extern "C" int ital_cross_cov_cols(const double* X, const double* xnorm, int64_t n, int ldx, const double* Xs,
                                    const double* sn, int c, const double* W, int ldw, const double* V, int64_t ldv,
                                    int m, double var, double length_scale, double* out, int64_t ldo,
                                    hipStream_t stream) {
-    KcolsArgs a = {};
-    a.X = X; a.xnorm = xnorm; a.n = n; a.ldx = ldx; a.Xs = Xs; a.sn = sn; a.c = c;
-    a.W = W; a.ldw = ldw; a.V = V; a.ldv = ldv; a.m = m;
-    a.var = var; a.s = -2.0 * length_scale * length_scale; a.mode = MODE_RAW; a.out = out; a.ldo = ldo;
-    return launch_kcols(a, stream, "ital_cross_cov_cols");
+    return ital_cross_cov_cols_t(X, xnorm, n, ldx, Xs, sn, c, W, ldw, V, ldv, m, var, length_scale, out, ldo, ITAL_INGEST_F64,
+                                 stream);
 }
 
 // ital_cross_cov_cols with the seed computation of the next greedy step riding along (round driver, round.hip).
-int ital_cross_cov_cols_seed(const double* X, const double* xnorm, int64_t n, int ldx, const double* Xs, const double* sn, int c,
-                             const double* W, int ldw, const double* V, int64_t ldv, int m, double var, double length_scale,
+int ital_cross_cov_cols_seed(const void* X, int xtype, const double* xnorm, int64_t n, int ldx, const double* Xs, const double* sn,
+                             int c, const double* W, int ldw, const double* V, int64_t ldv, int m, double var, double length_scale,
                              double* out, int64_t ldo, const ital::SeedArgs& seed, hipStream_t stream) {
     KcolsArgs a = {};
     a.X = X; a.xnorm = xnorm; a.n = n; a.ldx = ldx; a.Xs = Xs; a.sn = sn; a.c = c;
@@ -298,20 +340,38 @@ int ital_cross_cov_cols_seed(const double* X, const double* xnorm, int64_t n, in
     if (a.c < 1 || a.c > 16) return ital_fail(-22, "kcols: c must be in 1..16");
     if (a.m < 0 || (a.m > 0 && (!a.W || !a.V))) return ital_fail(-22, "kcols: W/V missing");
     const int64_t nk = (a.n + 63) / 64, ns = (seed.slab_n + 255) / 256;
-    ITAL_LAUNCH(kcols_seed_kernel, dim3((unsigned)(nk + ns)), dim3(256), 0, stream, a, seed, (unsigned)nk);
+    const dim3 blocks((unsigned)(nk + ns));
+    switch (xtype) {
+        case ITAL_INGEST_F64: ITAL_LAUNCH(kcols_seed_kernel, blocks, dim3(256), 0, stream, a, seed, (unsigned)nk); break;
+        case ITAL_INGEST_F32: ITAL_LAUNCH(kcols_rows_seed_kernel<IngestF32>, blocks, dim3(256), 0, stream, a, seed, (unsigned)nk); break;
+        case ITAL_INGEST_F16: ITAL_LAUNCH(kcols_rows_seed_kernel<IngestF16>, blocks, dim3(256), 0, stream, a, seed, (unsigned)nk); break;
+        case ITAL_INGEST_BF16: ITAL_LAUNCH(kcols_rows_seed_kernel<IngestBF16>, blocks, dim3(256), 0, stream, a, seed, (unsigned)nk); break;
+        default: return ital_fail(-22, "ital_cross_cov_cols_seed: unknown element type of X");
+    }
     return ital_check_launch("ital_cross_cov_cols_seed");
+}
+
+extern "C" int ital_whiten_append_t(const void* X, const double* xnorm, int64_t n, int ldx, const double* Xnew,
+                                    const double* snew, int c, const double* L21, int ldw, const double* L22,
+                                    const double* alpha_new, double* V, int64_t ldv, int m, double var, double length_scale,
+                                    double* mu, double* s2, int xtype, hipStream_t stream) {
+    const int rc = ital_rows_check(X, xtype, "ital_whiten_append: unknown element type of X",
+                                   "ital_whiten_append: X must be aligned to 16 B");
+    if (rc) return rc;
+    KcolsArgs a = {};
+    a.X = X; a.xnorm = xnorm; a.n = n; a.ldx = ldx; a.Xs = Xnew; a.sn = snew; a.c = c;
+    a.W = L21; a.ldw = ldw; a.V = V; a.Vw = V; a.ldv = ldv; a.m = m;
+    a.var = var; a.s = -2.0 * length_scale * length_scale; a.mode = MODE_WHITEN;
+    a.L22 = L22; a.alpha_new = alpha_new; a.mu = mu; a.s2 = s2;
+    return launch_kcols(a, xtype, stream, "ital_whiten_append");
 }
 
 extern "C" int ital_whiten_append(const double* X, const double* xnorm, int64_t n, int ldx, const double* Xnew,
                                   const double* snew, int c, const double* L21, int ldw, const double* L22,
                                   const double* alpha_new, double* V, int64_t ldv, int m, double var,
                                   double length_scale, double* mu, double* s2, hipStream_t stream) {
-    KcolsArgs a = {};
-    a.X = X; a.xnorm = xnorm; a.n = n; a.ldx = ldx; a.Xs = Xnew; a.sn = snew; a.c = c;
-    a.W = L21; a.ldw = ldw; a.V = V; a.Vw = V; a.ldv = ldv; a.m = m;
-    a.var = var; a.s = -2.0 * length_scale * length_scale; a.mode = MODE_WHITEN;
-    a.L22 = L22; a.alpha_new = alpha_new; a.mu = mu; a.s2 = s2;
-    return launch_kcols(a, stream, "ital_whiten_append");
+    return ital_whiten_append_t(X, xnorm, n, ldx, Xnew, snew, c, L21, ldw, L22, alpha_new, V, ldv, m, var, length_scale, mu, s2,
+                                ITAL_INGEST_F64, stream);
 }
 
 extern "C" int ital_predict(const double* Xt, int64_t nt, int ldx, const double* XT, const double* XTn, int m,

@@ -15,14 +15,16 @@
 #include "ital_hip.h"
 #include "ital_internal.h"
 #include "ital_rewhiten.h"
+#include "ital_rows.h"
+#include "rows_elem.h"
 
 namespace ital {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 struct RewhitenArgs {
-    const double* X;      // [n][ldx] the range
-    const double* xnorm;  // [n] (written by ital_row_norms before the first launch)
+    const void* X;        // [n][ldx] the range, of the element type the kernel is instantiated for (rows_elem.h)
+    const double* xnorm;  // [n] (FP64 rows: written by ital_row_norms before the first launch; narrower: the store's)
     int64_t n;
     int ldx;
     const double* XT;     // [m][ldx]
@@ -45,8 +47,10 @@ constexpr int REWHITEN_TILE = 16 * 17;         // the R[j][i] transpose buffer o
 // LDS doubles per wave: the chunk's whitened values [16 G][16], then the transpose buffer.
 template <int G> constexpr int rewhiten_wave_doubles() { return 16 * G * 16 + REWHITEN_TILE; }
 
-template <int G>
-__global__ __launch_bounds__(256) void whiten_rows_kernel(RewhitenArgs a) {
+// E: element type of X.  As in kcols_body only the fetch of the data rows depends on it (one vector load of a lane's four
+// features in X's type, widened exactly when the MFMA takes them).
+template <int G, class E>
+__device__ __forceinline__ void whiten_rows_body(const RewhitenArgs& a) {
     extern __shared__ double rewhiten_lds[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(256) void whiten_rows_kernel(RewhitenArgs a) {
     double* tile = vl + 16 * G * 16;                                  // tile[j * 17 + i]
     const int64_t irow = i0 + col;
     const bool row_ok = irow < a.n;
-    const double* xrow = a.X + (row_ok ? irow : 0) * a.ldx;
+    const typename E::raw* xrow = static_cast<const typename E::raw*>(a.X) + (row_ok ? irow : 0) * a.ldx;
     const int nb = (a.c1 - a.c0 + 15) >> 4;       // blocks of 16 labelled rows in this launch, 0..G
 
     // ---- dot products of the tile with every labelled row of the chunk: k ascending, 16 k-values per step; per element
@@ -67,16 +71,14 @@ __global__ __launch_bounds__(256) void whiten_rows_kernel(RewhitenArgs a) {
 #pragma unroll
     for (int g = 0; g < G; g++) acc_dot[g] = d4{0, 0, 0, 0};
     for (int k0 = 0; k0 < a.ldx; k0 += 32) {
-        double2 b01[2], b23[2], a01[2][G], a23[2][G];
+        Quads<E, 2> b;
+        double2 a01[2][G], a23[2][G];
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int kk = k0 + 16 * u + 4 * kg;
             const bool in = k0 + 16 * u < a.ldx;           // ldx is a multiple of 16
-            b01[u] = b23[u] = double2{0, 0};
-            if (in && row_ok) {
-                b01[u] = *reinterpret_cast<const double2*>(xrow + kk);
-                b23[u] = *reinterpret_cast<const double2*>(xrow + kk + 2);
-            }
+            b.zero(u);
+            if (in && row_ok) b.load(u, xrow + kk);
 #pragma unroll
             for (int g = 0; g < G; g++) {
                 a01[u][g] = a23[u][g] = double2{0, 0};
@@ -93,10 +95,10 @@ __global__ __launch_bounds__(256) void whiten_rows_kernel(RewhitenArgs a) {
 #pragma unroll
             for (int g = 0; g < G; g++) {
                 if (g < nb) {
-                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u][g].x, b01[u].x, acc_dot[g], 0, 0, 0);
-                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u][g].y, b01[u].y, acc_dot[g], 0, 0, 0);
-                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u][g].x, b23[u].x, acc_dot[g], 0, 0, 0);
-                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u][g].y, b23[u].y, acc_dot[g], 0, 0, 0);
+                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u][g].x, b.get(u, 0), acc_dot[g], 0, 0, 0);
+                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a01[u][g].y, b.get(u, 1), acc_dot[g], 0, 0, 0);
+                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u][g].x, b.get(u, 2), acc_dot[g], 0, 0, 0);
+                    acc_dot[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a23[u][g].y, b.get(u, 3), acc_dot[g], 0, 0, 0);
                 }
             }
         }
@@ -193,16 +195,33 @@ __global__ __launch_bounds__(256) void whiten_rows_kernel(RewhitenArgs a) {
 }
 
 template <int G>
-static int launch_whiten_rows(const RewhitenArgs& a, hipStream_t stream) {
-    static ItalLdsFlags flags;
+__global__ __launch_bounds__(256) void whiten_rows_kernel(RewhitenArgs a) { whiten_rows_body<G, IngestF64>(a); }
+
+// The same sweep over rows kept in their source precision (include/ital_rows.h); the FP64 kernel above keeps its name.
+template <int G, class E>
+__global__ __launch_bounds__(256) void whiten_typed_rows_kernel(RewhitenArgs a) { whiten_rows_body<G, E>(a); }
+
+template <int G, class E>
+static int launch_whiten_rows_of(const RewhitenArgs& a, void (*kernel)(RewhitenArgs), hipStream_t stream) {
+    static ItalLdsFlags flags;                    // one set per kernel: the attribute belongs to the function
     const int lds = 4 * rewhiten_wave_doubles<G>() * (int)sizeof(double);
     if (lds > 48 * 1024) {
-        const int rc = ital_raise_lds_limit(reinterpret_cast<const void*>(&whiten_rows_kernel<G>), lds, flags, "ital_whiten_rows");
+        const int rc = ital_raise_lds_limit(reinterpret_cast<const void*>(kernel), lds, flags, "ital_whiten_rows");
         if (rc) return rc;
     }
     const int64_t blocks = (a.n + 63) / 64;
-    ITAL_LAUNCH(whiten_rows_kernel<G>, dim3((unsigned)blocks), dim3(256), lds, stream, a);
+    ITAL_LAUNCH(kernel, dim3((unsigned)blocks), dim3(256), lds, stream, a);
     return ital_check_launch("ital_whiten_rows");
+}
+
+template <int G>
+static int launch_whiten_rows(const RewhitenArgs& a, int xtype, hipStream_t stream) {
+    switch (xtype) {
+        case ITAL_INGEST_F64: return launch_whiten_rows_of<G, IngestF64>(a, whiten_rows_kernel<G>, stream);
+        case ITAL_INGEST_F32: return launch_whiten_rows_of<G, IngestF32>(a, whiten_typed_rows_kernel<G, IngestF32>, stream);
+        case ITAL_INGEST_F16: return launch_whiten_rows_of<G, IngestF16>(a, whiten_typed_rows_kernel<G, IngestF16>, stream);
+        default: return launch_whiten_rows_of<G, IngestBF16>(a, whiten_typed_rows_kernel<G, IngestBF16>, stream);
+    }
 }
 
 }  // namespace ital
@@ -212,7 +231,12 @@ using namespace ital;
 extern "C" int ital_whiten_rows_chunk(void) { return REWHITEN_DEFAULT_CHUNK; }
 
 extern "C" int ital_whiten_rows(const ital_rewhiten_desc* d, hipStream_t stream) {
+    return ital_whiten_rows_t(d, ITAL_INGEST_F64, stream);
+}
+
+extern "C" int ital_whiten_rows_t(const ital_rewhiten_desc* d, int xtype, hipStream_t stream) {
     if (!d) return ital_fail(-22, "ital_whiten_rows: NULL descriptor");
+    if (rows_elem_size(xtype) == 0) return ital_fail(-22, "ital_whiten_rows: unknown element type of X");
     if (!d->X || !d->xnorm || !d->V || !d->mu || !d->s2) return ital_fail(-22, "ital_whiten_rows: X / xnorm / V / mu / s2 must all be given");
     if (d->n_rows < 0 || d->m < 0 || d->v_rows < 0) return ital_fail(-22, "ital_whiten_rows: negative size");
     if (d->n_rows > ((int64_t)1 << 36)) return ital_fail(-22, "ital_whiten_rows: more rows than one launch covers");
@@ -223,9 +247,11 @@ extern "C" int ital_whiten_rows(const ital_rewhiten_desc* d, hipStream_t stream)
     if (d->v_rows < d->m) return ital_fail(-22, "ital_whiten_rows: v_rows smaller than the labelled set");
     const int chunk = d->chunk ? d->chunk : REWHITEN_DEFAULT_CHUNK;
     if (chunk != 32 && chunk != 64 && chunk != 128) return ital_fail(-22, "ital_whiten_rows: chunk must be 0, 32, 64 or 128");
+    if (reinterpret_cast<uintptr_t>(d->X) % 16 != 0) return ital_fail(-22, "ital_whiten_rows: X must be aligned to 16 B");
     if (d->n_rows == 0) return 0;
-    int rc = ital_row_norms(d->X, d->n_rows, d->ldx, d->xnorm, stream);
-    if (rc) return rc;
+    int rc = 0;
+    // FP64 rows: the norms are part of the result.  Narrower rows: the store's xnorm already holds these bits (input only).
+    if (xtype == ITAL_INGEST_F64 && (rc = ital_row_norms(d->X, d->n_rows, d->ldx, d->xnorm, stream))) return rc;
     RewhitenArgs a = {};
     a.X = d->X; a.xnorm = d->xnorm; a.n = d->n_rows; a.ldx = d->ldx;
     a.XT = d->XT; a.XTn = d->XTn; a.L = d->L; a.ldl = d->ldl; a.alpha = d->alpha;
@@ -238,8 +264,8 @@ extern "C" int ital_whiten_rows(const ital_rewhiten_desc* d, hipStream_t stream)
         const bool last = a.c1 >= d->m;
         a.z0 = last ? d->m : 0;
         a.z1 = last ? d->v_rows : 0;
-        rc = chunk == 32 ? launch_whiten_rows<2>(a, stream) : chunk == 64 ? launch_whiten_rows<4>(a, stream)
-                                                                           : launch_whiten_rows<8>(a, stream);
+        rc = chunk == 32 ? launch_whiten_rows<2>(a, xtype, stream) : chunk == 64 ? launch_whiten_rows<4>(a, xtype, stream)
+                                                                                  : launch_whiten_rows<8>(a, xtype, stream);
         if (rc) return rc;
         c0 = a.c1;
     } while (c0 < d->m);

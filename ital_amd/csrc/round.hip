@@ -14,12 +14,14 @@
 
 #include "ital_hip.h"
 #include "ital_internal.h"
+#include "ital_rows.h"
 #include "qmc_seed.h"
+#include "rows_elem.h"
 
 // internal entry points of score.hip / rbf.hip
-int ital_score_step_internal(const ital_score_desc* d, hipStream_t stream, bool seeds_ready, ital::SeedArgs* seeds_only);
-int ital_cross_cov_cols_seed(const double* X, const double* xnorm, int64_t n, int ldx, const double* Xs, const double* sn, int c,
-                             const double* W, int ldw, const double* V, int64_t ldv, int m, double var, double length_scale,
+int ital_score_step_internal(const ital_score_desc* d, int xtype, hipStream_t stream, bool seeds_ready, ital::SeedArgs* seeds_only);
+int ital_cross_cov_cols_seed(const void* X, int xtype, const double* xnorm, int64_t n, int ldx, const double* Xs, const double* sn,
+                             int c, const double* W, int ldw, const double* V, int64_t ldv, int m, double var, double length_scale,
                              double* out, int64_t ldo, const ital::SeedArgs& seed, hipStream_t stream);
 
 namespace ital {
@@ -148,8 +150,15 @@ __global__ __launch_bounds__(1024) void compact_rearm_kernel(uint8_t* __restrict
 using namespace ital;
 
 extern "C" int ital_fetch_round(const ital_round_desc* r, hipStream_t stream) {
+    return ital_fetch_round_t(r, ITAL_INGEST_F64, stream);
+}
+
+extern "C" int ital_fetch_round_t(const ital_round_desc* r, int xtype, hipStream_t stream) {
     if (!r) return ital_fail(-22, "ital_fetch_round: null descriptor");
     const ital_score_desc& tpl = r->step;
+    const int trc = ital_rows_check(tpl.sel_X, xtype, "ital_fetch_round: unknown element type of step.sel_X",
+                                    "ital_fetch_round: step.sel_X must be aligned to 16 B");
+    if (trc) return trc;
     if (r->k < 1 || r->k > ITAL_MAX_T || r->k > tpl.batch.kmax) return ital_fail(-22, "ital_fetch_round: k outside 1..min(ITAL_MAX_T, kmax)");
     const bool ranks = r->world > 0;
     if (ranks && (!r->records_all || (!r->nccl_comm && !r->exchange)))
@@ -203,7 +212,7 @@ extern "C" int ital_fetch_round(const ital_round_desc* r, hipStream_t stream) {
     bool seeds_ready = false;
     for (int t = 1; t <= r->k; t++) {
         const ital_score_desc d = step_desc(t);
-        int rc = ital_score_step_internal(&d, stream, seeds_ready, nullptr);
+        int rc = ital_score_step_internal(&d, xtype, stream, seeds_ready, nullptr);
         if (rc) return rc;
         seeds_ready = false;
         if (ranks) {
@@ -223,15 +232,15 @@ extern "C" int ital_fetch_round(const ital_round_desc* r, hipStream_t stream) {
             // made and on nothing else) when that step runs in one slab of its workspace
             SeedArgs seed;
             const ital_score_desc nx = step_desc(t + 1);
-            if (ital_score_step_internal(&nx, stream, false, &seed) == 0) {
-                rc = ital_cross_cov_cols_seed(tpl.sel_X, tpl.sel_xnorm, r->n_rows, tpl.sel_ldx, xb, tpl.batch.XBn + slot, 1, vb,
+            if (ital_score_step_internal(&nx, xtype, stream, false, &seed) == 0) {
+                rc = ital_cross_cov_cols_seed(tpl.sel_X, xtype, tpl.sel_xnorm, r->n_rows, tpl.sel_ldx, xb, tpl.batch.XBn + slot, 1, vb,
                                               tpl.batch.ldw, tpl.sel_V, tpl.sel_ldv, tpl.sel_m, r->var, r->length_scale, col,
                                               tpl.ldc, seed, stream);
                 seeds_ready = true;
             } else {
-                rc = ital_cross_cov_cols(tpl.sel_X, tpl.sel_xnorm, r->n_rows, tpl.sel_ldx, xb, tpl.batch.XBn + slot, 1, vb,
-                                         tpl.batch.ldw, tpl.sel_V, tpl.sel_ldv, tpl.sel_m, r->var, r->length_scale, col, tpl.ldc,
-                                         stream);
+                rc = ital_cross_cov_cols_t(tpl.sel_X, tpl.sel_xnorm, r->n_rows, tpl.sel_ldx, xb, tpl.batch.XBn + slot, 1, vb,
+                                           tpl.batch.ldw, tpl.sel_V, tpl.sel_ldv, tpl.sel_m, r->var, r->length_scale, col, tpl.ldc,
+                                           xtype, stream);
             }
             if (rc) return rc;
         }

@@ -25,6 +25,7 @@
 #include "device_math.h"
 #include "ital_hip.h"
 #include "ital_internal.h"
+#include "ital_rows.h"
 #include "qmc_common.h"
 #include "qmc_exact.h"
 #include "qmc_seed.h"
@@ -941,7 +942,8 @@ extern "C" int64_t ital_sel_parts_len(int k, int64_t n_cand, int64_t work_double
 // seeds_ready: the generator states of the candidates are already in the workspace (the round driver computed them in the
 // launch of the covariance column before).  seeds_only != nullptr: nothing is launched -- the descriptor of the seed
 // computation of this step is returned (0), or 1 when the step needs several slabs (then the step seeds itself).
-int ital_score_step_internal(const ital_score_desc* d, hipStream_t stream, bool seeds_ready, ital::SeedArgs* seeds_only) {
+// xtype: element type of d->sel_X (ITAL_INGEST_*), read by the record gather of the fused selection alone.
+int ital_score_step_internal(const ital_score_desc* d, int xtype, hipStream_t stream, bool seeds_ready, ital::SeedArgs* seeds_only) {
     if (!d) return ital_fail(-22, "ital_score_step: null descriptor");
     if (seeds_only && (d->n_cand <= 0 || d->t < 3 || d->t > ITAL_MAX_T || !d->work || !d->jump)) return 1;
     if (d->n_cand <= 0) return 0;
@@ -961,7 +963,7 @@ int ital_score_step_internal(const ital_score_desc* d, hipStream_t stream, bool 
             return ital_fail(-22, "ital_score_step: fused selection: batch layout mismatch");
         a.sel.rec = {d->cand, d->pos_offset, d->gpos, d->row_offset, d->sel_rank, 0, 0, d->mu, d->s2, d->sel_X, d->sel_xnorm,
                      d->sel_ldx, d->sel_V, d->sel_ldv, d->sel_m, d->sel_ldw, d->C, d->ldc, d->t - 1, d->batch.kmax, nullptr,
-                     d->sel_record, d->status};
+                     d->sel_record, d->status, xtype};
         a.sel.slot = d->t - 1;
         a.sel.b = d->batch;
         a.sel.alive = const_cast<uint8_t*>(d->alive);
@@ -997,5 +999,12 @@ int ital_score_step_internal(const ital_score_desc* d, hipStream_t stream, bool 
 }
 
 extern "C" int ital_score_step(const ital_score_desc* d, hipStream_t stream) {
-    return ital_score_step_internal(d, stream, false, nullptr);
+    return ital_score_step_internal(d, ITAL_INGEST_F64, stream, false, nullptr);
+}
+
+extern "C" int ital_score_step_t(const ital_score_desc* d, int xtype, hipStream_t stream) {
+    const int rc = ital_rows_check(d ? d->sel_X : nullptr, xtype, "ital_score_step: unknown element type of sel_X",
+                                   "ital_score_step: sel_X must be aligned to 16 B");
+    if (rc) return rc;
+    return ital_score_step_internal(d, xtype, stream, false, nullptr);
 }

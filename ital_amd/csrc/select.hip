@@ -11,6 +11,7 @@
 #include "device_math.h"
 #include "ital_hip.h"
 #include "ital_internal.h"
+#include "ital_rows.h"
 #include "select_common.h"
 
 namespace ital {
@@ -76,11 +77,23 @@ extern "C" int ital_select_local(const double* mi, const int32_t* cand, const ui
                                  const double* mu, const double* s2, const double* X, const double* xnorm, int ldx,
                                  const double* V, int64_t ldv, int m, int ldw, const double* C, int64_t ldc, int nprev,
                                  int kmax, const int* status, double* work, double* record, hipStream_t stream) {
+    return ital_select_local_t(mi, cand, alive, n_cand, pos_offset, gpos, row_offset, rank, mode, mu, s2, X, xnorm, ldx, V, ldv, m,
+                               ldw, C, ldc, nprev, kmax, status, work, record, ITAL_INGEST_F64, stream);
+}
+
+extern "C" int ital_select_local_t(const double* mi, const int32_t* cand, const uint8_t* alive, int64_t n_cand,
+                                   int64_t pos_offset, const int64_t* gpos, int64_t row_offset, int rank, int mode,
+                                   const double* mu, const double* s2, const void* X, const double* xnorm, int ldx,
+                                   const double* V, int64_t ldv, int m, int ldw, const double* C, int64_t ldc, int nprev,
+                                   int kmax, const int* status, double* work, double* record, int xtype, hipStream_t stream) {
+    const int trc = ital_rows_check(X, xtype, "ital_select_local: unknown element type of X",
+                                    "ital_select_local: X must be aligned to 16 B");
+    if (trc) return trc;
     if (mode != 0 && mode != 1) return ital_fail(-22, "ital_select_local: mode must be 0 (argmax) or 1 (argmin)");
     if (m > ldw) return ital_fail(-22, "ital_select_local: m exceeds ldw");
     if (n_cand <= (1 << 18)) {
         RecordArgs a1 = {cand, pos_offset, gpos, row_offset, rank, mode, 0, mu, s2, X, xnorm, ldx, V, ldv, m, ldw,
-                         C, ldc, nprev, kmax, nullptr, record, status};
+                         C, ldc, nprev, kmax, nullptr, record, status, xtype};
         ITAL_LAUNCH(select_local_small_kernel, dim3(1), dim3(1024), 0, stream, mi, alive, n_cand, a1);
         return ital_check_launch("ital_select_local(small)");
     }
@@ -92,7 +105,7 @@ extern "C" int ital_select_local(const double* mi, const int32_t* cand, const ui
     int rc = ital_check_launch("ital_select_local(partial)");
     if (rc) return rc;
     RecordArgs a = {cand, pos_offset, gpos, row_offset, rank, mode, nparts, mu, s2, X, xnorm, ldx, V, ldv, m, ldw,
-                    C, ldc, nprev, kmax, work, record, status};
+                    C, ldc, nprev, kmax, work, record, status, xtype};
     ITAL_LAUNCH(select_record_kernel, dim3(1), dim3(256), 0, stream, a);
     return ital_check_launch("ital_select_local(record)");
 }
@@ -102,12 +115,24 @@ extern "C" int ital_select_fused(const double* mi, const int32_t* cand, uint8_t*
                                  const double* s2, const double* X, const double* xnorm, int ldx, const double* V, int64_t ldv,
                                  int m, int ldw, const double* C, int64_t ldc, int nprev, int slot, ital_batch batch,
                                  const int* status, double* record, int64_t* ret, hipStream_t stream) {
+    return ital_select_fused_t(mi, cand, alive, n_cand, pos_offset, gpos, row_offset, rank, mode, mu, s2, X, xnorm, ldx, V, ldv, m,
+                               ldw, C, ldc, nprev, slot, batch, status, record, ret, ITAL_INGEST_F64, stream);
+}
+
+extern "C" int ital_select_fused_t(const double* mi, const int32_t* cand, uint8_t* alive, int64_t n_cand, int64_t pos_offset,
+                                   const int64_t* gpos, int64_t row_offset, int rank, int mode, const double* mu,
+                                   const double* s2, const void* X, const double* xnorm, int ldx, const double* V, int64_t ldv,
+                                   int m, int ldw, const double* C, int64_t ldc, int nprev, int slot, ital_batch batch,
+                                   const int* status, double* record, int64_t* ret, int xtype, hipStream_t stream) {
+    const int trc = ital_rows_check(X, xtype, "ital_select_fused: unknown element type of X",
+                                    "ital_select_fused: X must be aligned to 16 B");
+    if (trc) return trc;
     if (mode != 0 && mode != 1) return ital_fail(-22, "ital_select_fused: mode must be 0 (argmax) or 1 (argmin)");
     if (m > ldw) return ital_fail(-22, "ital_select_fused: m exceeds ldw");
     if (slot < 0 || slot >= batch.kmax) return ital_fail(-22, "ital_select_fused: slot outside the batch capacity");
     if (ldx != batch.ldx || ldw != batch.ldw) return ital_fail(-22, "ital_select_fused: batch layout mismatch");
     RecordArgs a = {cand, pos_offset, gpos, row_offset, rank, mode, 0, mu, s2, X, xnorm, ldx, V, ldv, m, ldw,
-                    C, ldc, nprev, batch.kmax, nullptr, record, status};
+                    C, ldc, nprev, batch.kmax, nullptr, record, status, xtype};
     ITAL_LAUNCH(select_fused_kernel, dim3(1), dim3(1024), 0, stream, mi, n_cand, a, slot, batch, alive, ret);
     return ital_check_launch("ital_select_fused");
 }

@@ -7,6 +7,8 @@
 #include <stdint.h>
 
 #include "ital_hip.h"
+#include "ital_ingest.h"
+#include "rows_elem.h"
 
 namespace ital {
 
@@ -84,9 +86,10 @@ __device__ __forceinline__ Best scan_best(const double* __restrict__ mi, const u
 
 struct RecordArgs {
     const int32_t* cand; int64_t pos_offset; const int64_t* gpos; int64_t row_offset; int rank, mode, nparts;
-    const double *mu, *s2, *X, *xnorm; int ldx; const double* V; int64_t ldv; int m, ldw;
+    const double *mu, *s2; const void* X; const double* xnorm; int ldx; const double* V; int64_t ldv; int m, ldw;
     const double* C; int64_t ldc; int nprev, kmax;
     const double* work; double* record; const int* status;
+    int xtype;               // element type of X (ITAL_INGEST_*; 0 = FP64): the record itself is FP64 whatever X is
 };
 
 // Packs the record of the winner `v` (valid in thread 0 of the block).
@@ -117,7 +120,12 @@ static __device__ void record_body(const RecordArgs& a, Best v) {
         rec[8] = status;
         rec[9] = 0.0;
     }
-    for (int k = threadIdx.x; k < a.ldx; k += blockDim.x) rec[ITAL_REC_HEADER + k] = a.X[(int64_t)row * a.ldx + k];
+    switch (a.xtype) {         // the winner's feature row, widened (exactly) while it is copied
+        case ITAL_INGEST_F32: widen_row<IngestF32>(rec + ITAL_REC_HEADER, a.X, row, a.ldx); break;
+        case ITAL_INGEST_F16: widen_row<IngestF16>(rec + ITAL_REC_HEADER, a.X, row, a.ldx); break;
+        case ITAL_INGEST_BF16: widen_row<IngestBF16>(rec + ITAL_REC_HEADER, a.X, row, a.ldx); break;
+        default: widen_row<IngestF64>(rec + ITAL_REC_HEADER, a.X, row, a.ldx); break;
+    }
     for (int r = threadIdx.x; r < a.ldw; r += blockDim.x)
         rec[ITAL_REC_HEADER + a.ldx + r] = r < a.m ? a.V[(int64_t)r * a.ldv + row] : 0.0;
     for (int b = threadIdx.x; b < a.kmax; b += blockDim.x)

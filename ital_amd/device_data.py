@@ -77,6 +77,19 @@ def as_rows(data):
     return t
 
 
+def ingest_same(t, X, xnorm, scratch):
+    """Rows of the DEVICE tensor `t` -> X[i, :] (padded rows of t's OWN element type, bits kept) and xnorm[i] (FP64, the bits
+    ingest() gives), i < len(t), on the current stream (ital_ingest_rows_t).  scratch: [rows, ldx] float64 -- the FP64
+    expansion exists one block of that many rows at a time, for the norms alone."""
+    k, d = t.shape
+    if k == 0:
+        return
+    ld = t.stride(0) if k > 1 else d
+    check(_lib.lib().ital_ingest_rows_t(t.data_ptr(), DTYPE_CODES[t.dtype], k, d, ld, X.data_ptr(), X.shape[1], xnorm.data_ptr(),
+                                        0 if scratch is None else scratch.data_ptr(), 0 if scratch is None else scratch.shape[0],
+                                        _stream()))
+
+
 def ingest(t, X, xnorm):
     """Rows of the DEVICE tensor `t` (as as_rows() leaves it) -> X[i, :] (padded FP64) and xnorm[i], i < len(t), on the
     current stream.  X: [>= len(t), ldx] float64, contiguous; xnorm: [>= len(t)] float64."""
@@ -89,19 +102,30 @@ def ingest(t, X, xnorm):
 
 
 class DeviceData(object):
-    """n x d feature rows on `device` as padded FP64 rows `X` [n, ldx] and squared norms `xnorm` [n].
+    """n x d feature rows on `device` as padded rows `X` [n, ldx] -- FP64, or the source's own element type -- and FP64
+    squared norms `xnorm` [n].
 
     - data: 2-D numpy array or torch tensor, on the host or on a device; f16 / f32 / f64 (bf16 for tensors) travel and are
       converted in their own type, any other real dtype goes through float64.  A row-strided view (`T[:, 3:131]`) is read as
       it is.  The source is never aliased: afterwards the caller may free or overwrite it.
     - capacity: rows to make room for (at least n); `append` within it writes in place.
     - chunk_bytes: host data is uploaded in pieces of at most this size, each converted behind its upload.
+    - storage: "f64" (the default): padded FP64 rows.  "source": the rows stay in the element type as_rows() leaves them in
+      (f16, bf16, f32 or f64; nothing is ever narrowed) -- 2 or 4 bytes per feature instead of 8.  Every kernel that reads
+      whole rows widens the elements in registers (include/ital_rows.h), so a learner on a compact store computes, bit for
+      bit, what one on the FP64 store of the same values computes; `xnorm` holds the bits the FP64 store's has.  The FP64
+      expansion exists only as a scratch block of at most chunk_bytes while rows are written (for the norms).  `append`
+      takes rows of the store's element type.
     """
 
-    def __init__(self, data, *, device=None, capacity=None, chunk_bytes=256 << 20):
+    def __init__(self, data, *, storage="f64", device=None, capacity=None, chunk_bytes=256 << 20):
+        if storage not in ("f64", "source"):
+            raise ValueError("storage must be 'f64' or 'source', not %r" % (storage,))
         if not torch.cuda.is_available():
             raise RuntimeError("ital_amd.DeviceData needs a HIP device (no CPU fallback)")
         t = as_rows(data)
+        #: torch dtype of the stored rows
+        self.storage = t.dtype if storage == "source" else torch.float64
         self.device = torch.device(device if device is not None else "cuda:0")
         self.chunk_bytes = int(chunk_bytes)
         self.n = 0
@@ -115,7 +139,7 @@ class DeviceData(object):
     # ------------------------------------------------------------------ storage
     def _alloc(self, capacity):
         with torch.cuda.device(self.device):
-            X = torch.empty((capacity, self.ldx), dtype=torch.float64, device=self.device)
+            X = torch.empty((capacity, self.ldx), dtype=self.storage, device=self.device)
             xnorm = torch.empty(capacity, dtype=torch.float64, device=self.device)
             if self.n:
                 # the tensors left behind are not freed here: a learner that still views them keeps them, and its prefix
@@ -130,15 +154,23 @@ class DeviceData(object):
             return
         with torch.cuda.device(self.device):
             X, xnorm = self._X[self.n:], self._xnorm[self.n:]
+            write, scratch = ingest, None
+            if self.storage != torch.float64:
+                # the norms come from ital_ingest_rows on a bounded FP64 block (freed when this call returns)
+                scratch = torch.empty((max(1, min(k, self.chunk_bytes // (8 * self.ldx))), self.ldx), dtype=torch.float64,
+                                      device=self.device)
+
+                def write(piece, X, xnorm):
+                    ingest_same(piece, X, xnorm, scratch)
             if t.is_cuda:
                 if t.device != self.device:
                     t = t.to(self.device)
-                ingest(t, X, xnorm)
+                write(t, X, xnorm)
             else:
                 step = max(1, self.chunk_bytes // (self.d * t.element_size()))
                 for r0 in range(0, k, step):
                     piece = t[r0:r0 + step].contiguous().to(self.device)
-                    ingest(piece, X[r0:], xnorm[r0:])
+                    write(piece, X[r0:], xnorm[r0:])
         self.n += k
 
     # ------------------------------------------------------------------ what a learner and its caller read
@@ -164,12 +196,12 @@ class DeviceData(object):
     def rows(self, idx=None):
         """The rows (all, or those of the index list `idx`) as a float64 numpy array: downloaded on demand, not kept."""
         if idx is None:
-            return self._X[: self.n, : self.d].cpu().numpy()
+            return self._X[: self.n, : self.d].cpu().to(torch.float64).numpy()
         idx = np.asarray(idx, dtype=np.int64).reshape(-1)
         if len(idx) and (idx.min() < -self.n or idx.max() >= self.n):
             raise IndexError("row index outside the %d rows" % self.n)
         sel = torch.from_numpy(idx % max(self.n, 1)).to(self.device)
-        return self._X[: self.n].index_select(0, sel)[:, : self.d].cpu().numpy()
+        return self._X[: self.n].index_select(0, sel)[:, : self.d].to(torch.float64).cpu().numpy()
 
     def append(self, rows):
         """Adds rows (the input kinds of the constructor) as rows n .. n + k - 1 and returns k.  ValueError, with nothing
@@ -181,6 +213,9 @@ class DeviceData(object):
             return 0
         if t.shape[1] != self.d:
             raise ValueError("rows must be a k-by-%d array" % self.d)
+        if self.storage != torch.float64 and t.dtype != self.storage:
+            raise TypeError("this store keeps %s rows: append rows of that type (nothing is narrowed), not %s"
+                            % (self.storage, t.dtype))
         k = int(t.shape[0])
         if self.n + k > self.capacity:
             self._alloc(max(2 * self.capacity, self.n + k))

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib, sharding
 from ._lib import check
-from .device_data import DeviceData
+from .device_data import DTYPE_CODES, DeviceData
 
 
 def _pad16(v):
@@ -82,6 +82,9 @@ class GaussianProcess(object):
             data = DeviceData(data, device=self.device)
         self.store = data if isinstance(data, DeviceData) else None
         if self.store is not None:
+            if self.world > 1 and self.store.storage != torch.float64:
+                raise NotImplementedError("a compact store (DeviceData(storage='source'), %s rows) cannot be used by several "
+                                          "ranks: row sharding reads FP64 rows" % self.store.storage)
             if self.world > 1:
                 raise NotImplementedError("a DeviceData is not sharded: pass ShardedRows to several ranks")
             if self.store.device != self.device:
@@ -117,6 +120,9 @@ class GaussianProcess(object):
                 self.Xd = Xp
                 self.xnorm = torch.empty(max(self.n, 1), dtype=torch.float64, device=self.device)
                 check(self._lib.ital_row_norms(_ptr(self.Xd), self.n, self.ldx, _ptr(self.xnorm), _stream()))
+            # element type of Xd (the INGEST_* codes): FP64 unless the rows are views of a compact store, whose readers are
+            # the typed entry points of include/ital_rows.h
+            self.xtype = DTYPE_CODES[self.Xd.dtype]
             self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._gather_bufs = {}
             if capacity is None:
@@ -281,10 +287,11 @@ class GaussianProcess(object):
         """Feature rows of global indices, replicated on every rank (owners contribute, the rest adds zeros)."""
         if not self.collective:
             idx = torch.as_tensor(ind, dtype=torch.int64, device=self.device)
-            return self.Xd.index_select(0, idx)       # every row is local: no ownership test, no host synchronisation
+            # every row is local: no ownership test, no host synchronisation (a compact store's rows are widened: exact)
+            return self.Xd.index_select(0, idx).to(torch.float64)
         mask, loc, any_own = self._owned(ind)
         if any_own:
-            rows = self.Xd.index_select(0, loc) * mask[:, None]
+            rows = self.Xd.index_select(0, loc).to(torch.float64) * mask[:, None]
         else:
             rows = torch.zeros((len(ind), self.ldx), dtype=torch.float64, device=self.device)
         sharding.all_reduce_sum(rows, self.group)
@@ -327,11 +334,12 @@ class GaussianProcess(object):
         for j in range(c):
             a.lb.slot[j] = int(slots[j])
             a.lb.y[j] = float(y[j])
-        check(self._lib.ital_gp_append(ctypes.byref(a), _stream()))
+        check(_lib.rows_fn("ital_gp_append", self.xtype)(ctypes.byref(a), _stream()))
         self.m += c
 
     def _append(self, rows, y):
         lib, st = self._lib, _stream()
+        whiten_append = _lib.rows_fn("ital_whiten_append", self.xtype)
         c_total = rows.shape[0]
         if self.m + c_total > self.cap:
             self._alloc(max(2 * self.cap, self.m + c_total))
@@ -345,10 +353,10 @@ class GaussianProcess(object):
                                        _ptr(yd[c0:c0 + c]), m, c, float(self.var), float(self.length_scale),
                                        float(self.noise), _ptr(self.status), st))
             L21 = self.L[m:]
-            check(lib.ital_whiten_append(_ptr(self.Xd), _ptr(self.xnorm), self.n, self.ldx, _ptr(self.XT[m:m + c]),
-                                         _ptr(self.XTn[m:m + c]), c, _ptr(L21), self.cap,
-                                         L21.data_ptr() + 8 * m, _ptr(self.alpha[m:m + c]), _ptr(self.V), self.ldv, m,
-                                         float(self.var), float(self.length_scale), _ptr(self.mu), _ptr(self.s2), st))
+            check(whiten_append(_ptr(self.Xd), _ptr(self.xnorm), self.n, self.ldx, _ptr(self.XT[m:m + c]),
+                                _ptr(self.XTn[m:m + c]), c, _ptr(L21), self.cap,
+                                L21.data_ptr() + 8 * m, _ptr(self.alpha[m:m + c]), _ptr(self.V), self.ldv, m,
+                                float(self.var), float(self.length_scale), _ptr(self.mu), _ptr(self.s2), st))
             self.m += c
 
     def remove(self, ind):
@@ -396,14 +404,15 @@ class GaussianProcess(object):
     # ------------------------------------------------------------------ a live session: more rows, other hyper-parameters
     def _whiten_rows(self, row_start, n_rows):
         """xnorm, V[0:m], mu, s2 of the local rows [row_start, row_start + n_rows) against the whole current labelled set
-        (ital_whiten_rows: the feature rows are read ceil(m / chunk) times, not ceil(m / 16) times); rows m .. cap of V zero."""
+        (ital_whiten_rows: the feature rows are read ceil(m / chunk) times, not ceil(m / 16) times); rows m .. cap of V zero.
+        On a compact store xnorm is only read: the store wrote it with the rows."""
         r = _lib.ItalRewhitenDesc()
-        r.X, r.n_rows, r.ldx = self.Xd.data_ptr() + 8 * row_start * self.ldx, n_rows, self.ldx
+        r.X, r.n_rows, r.ldx = self.Xd.data_ptr() + self.Xd.element_size() * row_start * self.ldx, n_rows, self.ldx
         r.XT, r.XTn, r.L, r.ldl, r.alpha, r.m = _ptr(self.XT), _ptr(self.XTn), _ptr(self.L), self.cap, _ptr(self.alpha), self.m
         r.var, r.length_scale = float(self.var), float(self.length_scale)
         r.xnorm, r.V, r.ldv, r.v_rows = self.xnorm.data_ptr() + 8 * row_start, self.V.data_ptr() + 8 * row_start, self.ldv, self.cap
         r.mu, r.s2, r.chunk = self.mu.data_ptr() + 8 * row_start, self.s2.data_ptr() + 8 * row_start, 0
-        check(self._lib.ital_whiten_rows(ctypes.byref(r), _stream()))
+        check(_lib.rows_fn("ital_whiten_rows", self.xtype)(ctypes.byref(r), _stream()))
 
     def extend(self, rows):
         """Appends samples to the data matrix of a live model: they get the indices n_total .. n_total + len(rows) - 1.  The
@@ -748,9 +757,9 @@ class GaussianProcess(object):
         out = torch.empty((len(ind), self.ldv), dtype=torch.float64, device=self.device)
         for c0 in range(0, len(ind), 16):
             c = min(16, len(ind) - c0)
-            check(self._lib.ital_rbf_cols(_ptr(self.Xd), _ptr(self.xnorm), self.n, self.ldx, _ptr(rows[c0:c0 + c]),
-                                          _ptr(norms[c0:c0 + c]), c, float(self.var), float(self.length_scale),
-                                          _ptr(out[c0:c0 + c]), self.ldv, _stream()))
+            check(_lib.rows_fn("ital_rbf_cols", self.xtype)(_ptr(self.Xd), _ptr(self.xnorm), self.n, self.ldx,
+                                                            _ptr(rows[c0:c0 + c]), _ptr(norms[c0:c0 + c]), c, float(self.var),
+                                                            float(self.length_scale), _ptr(out[c0:c0 + c]), self.ldv, _stream()))
         return out[:, : self.n]
 
     def predict(self, X, cov_mode=None):

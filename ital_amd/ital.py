@@ -348,7 +348,7 @@ class ITAL(ActiveRetrievalBase):
                 fused = not gp.collective and 0 < n_loc <= (_FUSED_SELECT_MAX if tail else _FUSED_LAUNCH_MAX)
                 desc = self._step_desc(b, scored, t, k, n_alive, tail, fused)
                 ev0 = self._mark() if t < 3 else None
-                check(lib.ital_score_step(ctypes.byref(desc), st))
+                check(_lib.rows_fn("ital_score_step", gp.xtype)(ctypes.byref(desc), st))
                 if t < 3:
                     self._mark("score", t, n_alive, ev0)
                 if self.keep_scores:

@@ -100,9 +100,9 @@ class MCMI_min(ActiveRetrievalBase):
         # one launch: rows, whitened columns, norms, means and variances of the listed samples (zeros for samples of other
         # ranks); the list travels as one small upload
         cand_d = torch.from_numpy(np.ascontiguousarray(cand, dtype=np.int64)).to(dev)
-        check(_lib.lib().ital_gather_block(_ptr(cand_d), nc, gp.row0, gp.n, _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx, _ptr(gp.V),
-                                           gp.ldv, gp.m, _ptr(gp.mu), _ptr(gp.s2), _ptr(Xc), _ptr(Vc), ldc, _ptr(vec[0]),
-                                           _ptr(vec[1]), _ptr(vec[2]), _stream()))
+        check(_lib.rows_fn("ital_gather_block", gp.xtype)(_ptr(cand_d), nc, gp.row0, gp.n, _ptr(gp.Xd), _ptr(gp.xnorm), gp.ldx,
+                                                          _ptr(gp.V), gp.ldv, gp.m, _ptr(gp.mu), _ptr(gp.s2), _ptr(Xc), _ptr(Vc), ldc,
+                                                          _ptr(vec[0]), _ptr(vec[1]), _ptr(vec[2]), _stream()))
         if gp.collective:
             for buf in (Xc, Vc, vec):
                 sharding.all_reduce_sum(buf, gp.group)
