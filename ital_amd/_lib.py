@@ -1,6 +1,6 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
-include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_ingest.h and
-include/ital_rows.h).
+include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_ingest.h,
+include/ital_rows.h and include/ital_compact.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -276,6 +276,15 @@ ROWS_SIGNATURES = dict(
                                      c_void_p]))])
 
 
+#: deleting data rows: the gathers of the survivors' rows and of their columns of V, mu, s2, declared in include/ital_compact.h
+COMPACT_SIGNATURES = {
+    "ital_compact_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    "ital_compact_cols": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -296,7 +305,8 @@ def load(path=LIB_PATH):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
-            list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()):
+            list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
+            list(COMPACT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -8,10 +8,16 @@ object of its own, so that
     without a float64 copy on the host and without an n x d FP64 staging tensor on the device (ital_ingest_rows converts,
     pads and norms; host data travels in its own type, in pieces of at most `chunk_bytes`);
   - several learners over one database view the same rows (`GaussianProcess(data=store)` uploads nothing);
-  - it grows in place (`append`), and each learner catches up when it chooses to (`sync_data`).
+  - it grows in place (`append`), and each learner catches up when it chooses to (`sync_data`);
+  - rows leave it (`remove`): the survivors are gathered into fresh tensors (ital_compact_rows), and a change log of a few
+    integers per event tells each learner what happened since it last looked.
+
+The index arithmetic of a removal -- the map old index -> new index, its composition over several events, the remapping of
+id sets -- is in plain functions below, which need no device.
 
 One host thread drives a store and its learners; everything runs on the current torch stream of the store's device.
 """
+import bisect
 import warnings
 
 import numpy as np
@@ -101,6 +107,80 @@ def ingest(t, X, xnorm):
                                       _stream()))
 
 
+# ---------------------------------------------------------------------------------------------------- index arithmetic
+def normalize_ids(ids, n):
+    """`ids` (any iterable of ints; negative ones count from the end of the n rows) as an ascending list of distinct python
+    ints in [0, n).  IndexError for an id outside the rows."""
+    out = set()
+    for i in ids:
+        i = int(i)
+        if not -n <= i < n:
+            raise IndexError("row index %d outside the %d rows" % (i, n))
+        out.add(i + n if i < 0 else i)
+    return sorted(out)
+
+
+def keep_indices(n, removed):
+    """The survivors of removing the ascending, distinct ids `removed` from n rows: ascending int64 array."""
+    return np.delete(np.arange(n, dtype=np.int64), np.asarray(removed, dtype=np.int64))
+
+
+def removal_map(n, removed):
+    """The index map of one removal: int64 array of length n with the new index of every row, -1 for a removed one."""
+    out = np.full(n, -1, dtype=np.int64)
+    keep = keep_indices(n, removed)
+    out[keep] = np.arange(len(keep), dtype=np.int64)
+    return out
+
+
+def compose_maps(first, second):
+    """The map of `first` followed by `second` (`second` may be longer than first's survivors: rows appended in between are
+    not in the domain of the result)."""
+    first, second = np.asarray(first, dtype=np.int64), np.asarray(second, dtype=np.int64)
+    out = np.full(len(first), -1, dtype=np.int64)
+    alive = first >= 0
+    out[alive] = second[first[alive]]
+    return out
+
+
+def log_index_map(events, n):
+    """The composed index map of the rows 0 .. n - 1 over `events` (the entries of DeviceData.log) and the row count after
+    them: (int64 array of length n, n_after).  ValueError for a log that does not start at n rows."""
+    out = np.arange(n, dtype=np.int64)
+    for ev in events:
+        if ev[0] == "append":
+            n += int(ev[1])
+        elif ev[0] == "remove":
+            if ev[2] != n:
+                raise ValueError("the log removes from %d rows where there are %d" % (ev[2], n))
+            out = compose_maps(out, removal_map(n, ev[1]))
+            n -= len(ev[1])
+        else:
+            raise ValueError("unknown event %r" % (ev[0],))
+    return out, n
+
+
+def remap_ids(ids, removed):
+    """The ids of `ids` that survive the removal of the ascending list `removed`, under their new numbers, as a set: an id
+    moves down by the number of removed ids below it (bisection: O(|ids| log |removed|), nothing N-sized)."""
+    out = set()
+    for i in ids:
+        i = int(i)
+        at = bisect.bisect_left(removed, i)
+        if at < len(removed) and removed[at] == i:
+            continue
+        out.add(i - at)
+    return out
+
+
+def compact_rows(X, xnorm, n, keep, X_dst, xnorm_dst, status=None):
+    """X_dst[j] <- X[keep[j]], xnorm_dst[j] <- xnorm[keep[j]] (bits kept) for the device index array `keep`, on the current
+    stream (ital_compact_rows).  X, X_dst: padded rows of one of the four element types."""
+    check(_lib.lib().ital_compact_rows(X.data_ptr(), xnorm.data_ptr(), n, X.shape[1], DTYPE_CODES[X.dtype], keep.data_ptr(),
+                                       keep.shape[0], X_dst.data_ptr(), xnorm_dst.data_ptr(),
+                                       0 if status is None else status.data_ptr(), _stream()))
+
+
 class DeviceData(object):
     """n x d feature rows on `device` as padded rows `X` [n, ldx] -- FP64, or the source's own element type -- and FP64
     squared norms `xnorm` [n].
@@ -133,6 +213,9 @@ class DeviceData(object):
         if self.d < 1:
             raise ValueError("data must have at least one column")
         self.ldx = _pad16(self.d)
+        #: the change log: ("append", k) and ("remove", ascending removed ids, n before) in order; `epoch` == len(log).  A
+        #: learner remembers the epoch it has seen and walks the log from there (GaussianProcess.sync_data).
+        self.log, self.epoch = [], 0
         self._alloc(max(int(t.shape[0]), int(capacity or 0), 1))
         self._write(t)
 
@@ -220,4 +303,39 @@ class DeviceData(object):
         if self.n + k > self.capacity:
             self._alloc(max(2 * self.capacity, self.n + k))
         self._write(t)
+        self._record(("append", k))
         return k
+
+    def _record(self, event):
+        self.log.append(event)
+        self.epoch += 1
+
+    def _compact(self, keep):
+        """The rows `keep` (ascending int64 numpy array) gathered into fresh tensors of the same capacity, which become the
+        store's; the old ones are not freed here -- a learner that still views them keeps them, and its rows."""
+        with torch.cuda.device(self.device):
+            keep_d = torch.from_numpy(keep).to(self.device)
+            X = torch.empty((self.capacity, self.ldx), dtype=self.storage, device=self.device)
+            xnorm = torch.empty(self.capacity, dtype=torch.float64, device=self.device)
+            compact_rows(self._X, self._xnorm, self.n, keep_d, X, xnorm)       # the ids were checked on the host
+        self._X, self._xnorm, self.n = X, xnorm, len(keep)
+
+    def remove(self, ids):
+        """Deletes rows like np.delete(X, ids, axis=0): the survivors keep their order and get the indices 0 .. n - r - 1.
+        Returns the index map: an int64 array of the old length with the new index of every row, -1 for a removed one.  `ids`:
+        any iterable of ints; duplicates are collapsed, negative indices count from the end as in rows().  An empty list is a
+        no-op that returns the identity.  IndexError for an id outside the rows, ValueError for removing every row; nothing is
+        changed then.
+
+        Never writes to tensors a learner may view: the survivors are gathered (ital_compact_rows, bits kept) into a fresh
+        allocation of the same capacity that is swapped in, as when append() outgrows the capacity.  A learner that has not
+        called sync_data() since goes on, consistently, on the rows it knows."""
+        n = self.n
+        removed = normalize_ids(ids, n)
+        if not removed:
+            return np.arange(n, dtype=np.int64)
+        if len(removed) == n:
+            raise ValueError("remove() would leave no row")
+        self._compact(keep_indices(n, removed))
+        self._record(("remove", removed, n))
+        return removal_map(n, removed)

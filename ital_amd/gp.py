@@ -81,6 +81,9 @@ class GaussianProcess(object):
                 raise NotImplementedError("a tensor is kept as a DeviceData, which is not sharded: pass ShardedRows to several ranks")
             data = DeviceData(data, device=self.device)
         self.store = data if isinstance(data, DeviceData) else None
+        #: the epoch of the store's change log this model has seen (sync_data), and what its last call found there
+        self._epoch = self.store.epoch if self.store is not None else 0
+        self.last_index_map, self.last_removals = None, []
         if self.store is not None:
             if self.world > 1 and self.store.storage != torch.float64:
                 raise NotImplementedError("a compact store (DeviceData(storage='source'), %s rows) cannot be used by several "
@@ -402,15 +405,17 @@ class GaussianProcess(object):
         return self
 
     # ------------------------------------------------------------------ a live session: more rows, other hyper-parameters
-    def _whiten_rows(self, row_start, n_rows):
+    def _whiten_rows(self, row_start, n_rows, x_row_start=None):
         """xnorm, V[0:m], mu, s2 of the local rows [row_start, row_start + n_rows) against the whole current labelled set
         (ital_whiten_rows: the feature rows are read ceil(m / chunk) times, not ceil(m / 16) times); rows m .. cap of V zero.
-        On a compact store xnorm is only read: the store wrote it with the rows."""
+        On a compact store xnorm is only read: the store wrote it with the rows.  x_row_start: where the feature rows and
+        their norms stand in Xd / xnorm, if not at row_start (sync_data, while it walks a log)."""
+        x0 = row_start if x_row_start is None else x_row_start
         r = _lib.ItalRewhitenDesc()
-        r.X, r.n_rows, r.ldx = self.Xd.data_ptr() + self.Xd.element_size() * row_start * self.ldx, n_rows, self.ldx
+        r.X, r.n_rows, r.ldx = self.Xd.data_ptr() + self.Xd.element_size() * x0 * self.ldx, n_rows, self.ldx
         r.XT, r.XTn, r.L, r.ldl, r.alpha, r.m = _ptr(self.XT), _ptr(self.XTn), _ptr(self.L), self.cap, _ptr(self.alpha), self.m
         r.var, r.length_scale = float(self.var), float(self.length_scale)
-        r.xnorm, r.V, r.ldv, r.v_rows = self.xnorm.data_ptr() + 8 * row_start, self.V.data_ptr() + 8 * row_start, self.ldv, self.cap
+        r.xnorm, r.V, r.ldv, r.v_rows = self.xnorm.data_ptr() + 8 * x0, self.V.data_ptr() + 8 * row_start, self.ldv, self.cap
         r.mu, r.s2, r.chunk = self.mu.data_ptr() + 8 * row_start, self.s2.data_ptr() + 8 * row_start, 0
         check(_lib.rows_fn("ital_whiten_rows", self.xtype)(ctypes.byref(r), _stream()))
 
@@ -460,36 +465,192 @@ class GaussianProcess(object):
             self._replicate_mean()
         return self
 
+    # ------------------------------------------------------------------ a live session: rows leave
+    def _compact_cols(self, keep):
+        """V, mu, s2 <- their columns `keep` (ascending int64 numpy array of local rows) in new tensors with the leading
+        dimension of len(keep) rows (ital_compact_cols: bits kept, V zero outside [0:m, 0:len(keep))); n, n_total, row1 and
+        ldv follow.  Xd and xnorm are the caller's business.  The status word collects an index outside the rows."""
+        n_new, dev = len(keep), self.device
+        ldv = _pad16(max(n_new, 1))
+        keep_d = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.int64)).to(dev)
+        V = torch.empty((self.cap, ldv), dtype=torch.float64, device=dev)
+        mu = torch.zeros(max(n_new, 1), dtype=torch.float64, device=dev) if n_new == 0 else \
+            torch.empty(n_new, dtype=torch.float64, device=dev)
+        s2 = torch.full((1,), float(self.var), dtype=torch.float64, device=dev) if n_new == 0 else \
+            torch.empty(n_new, dtype=torch.float64, device=dev)
+        check(self._lib.ital_compact_cols(_ptr(self.V), self.ldv, self.m, _ptr(self.mu), _ptr(self.s2), self.n, _ptr(keep_d),
+                                          n_new, _ptr(V), ldv, self.cap, _ptr(mu), _ptr(s2), _ptr(self.status), _stream()))
+        self.V, self.mu, self.s2, self.ldv = V, mu, s2, ldv
+        self.n_total -= self.n - n_new
+        self.n = n_new
+        self.row1 = self.row0 + n_new
+        self._append_desc = None              # it holds X, xnorm, n and ldv
+        self._gather_bufs = {}
+        return keep_d
+
+    def _renumber(self, removed):
+        """`ind` after the data rows `removed` (ascending, none of them labelled any more) have left: data rows move down by
+        the number of removed rows below them, query rows by all of them."""
+        import bisect
+        self.ind = [i - bisect.bisect_left(removed, i) for i in self.ind]
+
+    def drop_rows(self, ids):
+        """Deletes samples from the data matrix of a live model that owns its rows, like np.delete(X, ids, axis=0): the
+        survivors keep their order and get the indices 0 .. n_total - r - 1.  The labelled ones among `ids` first leave the
+        model through remove() (a Cholesky row deletion and one sweep each, in that method's order); what is left is a gather
+        without arithmetic -- Xd, xnorm (ital_compact_rows) and V, mu, s2 (ital_compact_cols, into tensors with the new leading
+        dimension) keep the bits of every survivor.  `ind` is renumbered: query rows move down by the number of removed rows.
+        The reference has no such call: its dense K_all (gp.py:128) is built once.
+
+        `ids`: any iterable of ints; duplicates are collapsed, negative ones count from the end.  An empty list is a no-op.
+        ValueError (nothing changed) for a query row or any id >= n_total and for removing every row, IndexError for one
+        below -n_total; NotImplementedError on several ranks: row sharding cannot shrink yet.  On a DeviceData:
+        store.remove(ids), then sync_data()."""
+        from .device_data import compact_rows, keep_indices
+        if self.world > 1 or (self.store is None and not isinstance(self.X_host, np.ndarray)):
+            raise NotImplementedError("row sharding cannot shrink yet: drop_rows() needs all rows on one rank")
+        if self.store is not None:
+            raise ValueError("this model views the rows of a DeviceData: store.remove(ids), then sync_data()")
+        n = self.n_total
+        removed = set()
+        for i in ids:
+            i = int(i)
+            if i >= n:
+                raise ValueError("%d is a query row or outside the %d samples: it cannot be removed" % (i, n))
+            if i < -n:
+                raise IndexError("row index %d outside the %d rows" % (i, n))
+            removed.add(i + n if i < 0 else i)
+        removed = sorted(removed)
+        if not removed:
+            return self
+        if len(removed) == n:
+            raise ValueError("drop_rows() would leave no row")
+        labelled = set(self.ind)
+        labelled = [i for i in removed if i in labelled]
+        with torch.cuda.device(self.device):
+            if labelled:
+                self.remove(labelled)
+            keep = keep_indices(n, removed)
+            n_old, Xd_old, xnorm_old = self.n, self.Xd, self.xnorm
+            keep_d = self._compact_cols(keep)
+            self.Xd = torch.empty((len(keep), self.ldx), dtype=Xd_old.dtype, device=self.device)
+            self.xnorm = torch.empty(len(keep), dtype=torch.float64, device=self.device)
+            compact_rows(Xd_old, xnorm_old, n_old, keep_d, self.Xd, self.xnorm, self.status)
+            self.X_host = np.delete(self.X_host, removed, 0)
+            self._renumber(removed)
+            self._replicate_mean()
+            self.check_status()
+        return self
+
+    def _grow_to_store(self, x_row0, k):
+        """What sync_data() does for k appended rows: V (new leading dimension), mu and s2 grow by device-to-device copies
+        and the new columns n .. n + k - 1 alone are whitened against the labelled set (ital_whiten_rows) -- from the rows
+        x_row0 .. x_row0 + k - 1 of the store as it is NOW, which is where rows appended earlier in the log have moved to
+        when rows below them have left since (x_row0 == n when none did)."""
+        n_old, n_new, m, dev = self.n, self.n + k, self.m, self.device
+        ldv = _pad16(n_new)
+        mu = torch.empty(n_new, dtype=torch.float64, device=dev)
+        s2 = torch.empty(n_new, dtype=torch.float64, device=dev)
+        V = torch.zeros((self.cap, ldv), dtype=torch.float64, device=dev)
+        mu[:n_old], s2[:n_old] = self.mu[:n_old], self.s2[:n_old]
+        if m and n_old:
+            V[:m, :n_old] = self.V[:m, :n_old]
+        self.Xd, self.xnorm, self.mu, self.s2, self.V = self.store.X, self.store.xnorm, mu, s2, V
+        self.n, self.ldv = n_new, ldv
+        self.ind = [i + k if i >= self.n_total else i for i in self.ind]
+        self.n_total += k
+        self.row1 = self.row0 + n_new
+        self._append_desc = None          # it holds X, xnorm, n and ldv
+        self._gather_bufs = {}
+        self._whiten_rows(n_old, k, x_row0)       # writes the new rows' xnorm again: the bits the store already holds
+
     def sync_data(self):
-        """Catches up with the growth of the DeviceData this model was built on: what extend() does, minus the growth of Xd
-        and xnorm -- new views up to store.n; V (new leading dimension), mu and s2 grow by device-to-device copies; the new
-        range alone is whitened against the labelled set (ital_whiten_rows); the means are replicated; query rows move up in
-        `ind`.  Returns the number of rows gained; 0 changes nothing.  Until it is called the model goes on on its own n rows,
-        also across a reallocation of the store (its views keep the old tensors alive).  ValueError without a DeviceData."""
+        """Catches up with the DeviceData this model was built on: walks the store's change log from the epoch this model has
+        seen and applies its events in order.
+
+        - Appended rows: what extend() does, minus the growth of Xd and xnorm -- V (new leading dimension), mu and s2 grow by
+          device-to-device copies, the new range alone is whitened against the labelled set (ital_whiten_rows), query rows
+          move up in `ind`.  Appends that follow one another are taken in as one range.
+        - Removed rows: the labelled ones among them leave through remove() (a Cholesky row deletion and a sweep each), then V,
+          mu and s2 are gathered (ital_compact_cols: no arithmetic), `ind` is renumbered.
+        A row that was appended AND removed within the walked part of the log never enters the model; one that was appended
+        and stayed is whitened from where it stands in the store now.  At the end Xd and xnorm are views of the store's rows
+        and the means are replicated.
+
+        Returns the number of rows gained (0: nothing was appended, or nothing of it is left).  `last_index_map` is the
+        composed index map of the removals this call applied (int64 array of the old length: new index, or -1), None if there
+        were none; `last_removals` their ascending id lists, each in the numbering the model had when it was applied.  Until
+        sync_data() is called the model goes on on its own n rows, also across a reallocation of the store (its views keep the
+        old tensors alive).  ValueError without a DeviceData."""
         if self.store is None:
             raise ValueError("this model owns its rows: build it on a DeviceData to share and grow them")
-        n_old, n_new, m, dev = self.n, self.store.n, self.m, self.device
-        k = n_new - n_old
-        if k == 0:
+        store = self.store
+        events = store.log[self._epoch:store.epoch]
+        self.last_index_map, self.last_removals = None, []
+        if not events:
             return 0
-        ldv = _pad16(n_new)
-        with torch.cuda.device(dev):
-            mu = torch.empty(n_new, dtype=torch.float64, device=dev)
-            s2 = torch.empty(n_new, dtype=torch.float64, device=dev)
-            V = torch.zeros((self.cap, ldv), dtype=torch.float64, device=dev)
-            mu[:n_old], s2[:n_old] = self.mu[:n_old], self.s2[:n_old]
-            if m and n_old:
-                V[:m, :n_old] = self.V[:m, :n_old]
-            self.Xd, self.xnorm, self.mu, self.s2, self.V = self.store.X, self.store.xnorm, mu, s2, V
-            self.n, self.ldv = n_new, ldv
-            self.ind = [i + k if i >= self.n_total else i for i in self.ind]
-            self.n_total += k
-            self.row1 = self.row0 + n_new
-            self._append_desc = None          # it holds X, xnorm, n and ldv
-            self._gather_bufs = {}
-            self._whiten_rows(n_old, k)       # writes the new rows' xnorm again: the bits the store already holds
+        # first pass, on the host: which of the rows appended in these events are still there at the end (by serial number)
+        n0 = self.n
+        serial, born = np.zeros(0, dtype=np.int64), 0
+        old = n0
+        for ev in events:
+            if ev[0] == "append":
+                serial = np.concatenate((serial, np.arange(born, born + ev[1], dtype=np.int64)))
+                born += ev[1]
+            else:
+                ids = np.asarray(ev[1], dtype=np.int64)
+                if ev[2] != old + len(serial):
+                    raise RuntimeError("the store's log and this model's row count disagree")
+                serial = np.delete(serial, ids[ids >= old] - old)
+                old -= int((ids < old).sum())
+        survivors = serial                      # ascending; survivor t stands in row `old + t` of the store now
+        if old + len(survivors) != store.n:
+            raise RuntimeError("the store's log and its row count disagree")
+        alive = None                            # original indices of this model's first rows that are still there
+        gained, born, pending, a = 0, 0, 0, n0
+        with torch.cuda.device(self.device):
+            def take_in():
+                nonlocal pending, gained
+                # the rows born in [born - pending, born) that survive: a contiguous range of the store's tail
+                lo, hi = np.searchsorted(survivors, (born - pending, born))
+                if hi > lo:
+                    self._grow_to_store(old + int(lo), int(hi - lo))
+                    gained += int(hi - lo)
+                pending = 0
+
+            for ev in events:
+                if ev[0] == "append":
+                    born += ev[1]
+                    pending += ev[1]
+                    continue
+                take_in()
+                removed = [i for i in ev[1] if i < a]      # the rest never entered the model
+                if not removed:
+                    continue
+                if alive is None:
+                    alive = np.arange(n0, dtype=np.int64)
+                labelled = set(self.ind)
+                labelled = [i for i in removed if i in labelled]
+                if labelled:
+                    self.remove(labelled)
+                # the model's rows: the a rows it had before the walk that are left, then the survivors taken in so far
+                self._compact_cols(np.delete(np.arange(self.n, dtype=np.int64), np.asarray(removed, dtype=np.int64)))
+                self._renumber(removed)
+                alive = np.delete(alive, np.asarray(removed, dtype=np.int64))
+                a -= len(removed)
+                self.last_removals.append(removed)
+            take_in()
+            self.Xd, self.xnorm = store.X, store.xnorm
+            self._epoch = store.epoch
+            if alive is not None:
+                self.last_index_map = np.full(n0, -1, dtype=np.int64)
+                self.last_index_map[alive] = np.arange(len(alive), dtype=np.int64)
+            if self.n != store.n:
+                raise RuntimeError("the store's log and this model's row count disagree")
             self._replicate_mean()
-        return k
+            if alive is not None:
+                self.check_status()
+        return gained
 
     def clone(self):
         """A second model on the same DeviceData in this model's state: same row count (also when the store has grown since),

@@ -378,14 +378,70 @@ class ActiveRetrievalBase(object):
     def sync_data(self):
         """A learner on a DeviceData takes in the rows the store has gained since its construction or its last sync_data()
         (GaussianProcess.sync_data: only the new range is whitened): they get the ids that follow and are unseen; feedback,
-        `rounds` and both random streams stay as they are.  Returns the number of rows gained (0: nothing is touched).
-        ValueError for a learner that owns its rows."""
+        `rounds` and both random streams stay as they are.  Rows the store has lost since (DeviceData.remove) leave the
+        learner too, in the order of the store's change log: a labelled one as revoke() takes it out, the others by a gather;
+        removed ids vanish from the three id sets, the surviving ids are renumbered, and `last_index_map` is the composed
+        map.  Returns the number of rows gained (0 and no removal: nothing is touched).  ValueError for a learner that owns
+        its rows."""
         if not isinstance(self.data, DeviceData):
             raise ValueError("this learner owns its rows: build it on a DeviceData to share and grow them")
         k = self.gp.sync_data()
-        if k:
+        for removed in self.gp.last_removals:
+            self._ids_after_removal(removed)
+        if k or self.gp.last_removals:
+            self._fitted = self.gp.m > 0
             self._start_afresh()
         return k
+
+    @property
+    def last_index_map(self):
+        """The composed index map of the removals the last sync_data() applied (int64 array of the length the learner had:
+        the new index of every sample, -1 for a removed one); None if it applied none."""
+        return self.gp.last_index_map
+
+    def _ids_after_removal(self, removed):
+        """The three id sets once the samples `removed` (ascending) have left: they vanish from the sets, the surviving ids
+        move down (bisection on `removed`: nothing N-sized).  New sets are assigned: the unseen list and a device candidate
+        list rebuild on their next use."""
+        from .device_data import remap_ids
+        self.relevant_ids = remap_ids(self.relevant_ids, removed)
+        self.irrelevant_ids = remap_ids(self.irrelevant_ids, removed)
+        self.unnameable_ids = remap_ids(self.unnameable_ids, removed)
+
+    def remove_data(self, ids):
+        """Deletes samples from a live session, like np.delete(data, ids, axis=0): the survivors keep their order and get the
+        ids 0 .. n - r - 1; returns the index map (int64 array of the old length: the new id of every sample, -1 for a
+        removed one).  Removed ids vanish from the relevant / irrelevant / unnameable ids, the surviving ids are renumbered;
+        a labelled sample among `ids` first leaves the GP as revoke() takes it out (a Cholesky row deletion and one sweep),
+        everything else is a gather on the device that changes no bit of a survivor (GaussianProcess.drop_rows).  `rounds` and
+        both random streams stay as they are.  The reference would need a new learner (and a new dense K_all, gp.py:128).
+
+        `ids`: any iterable of ints; duplicates are collapsed, negative ones count from the end; an empty list is a no-op
+        that returns the identity.  ValueError / IndexError (nothing changed) for a query row or an id outside the samples and
+        for removing every sample; NotImplementedError on several ranks: row sharding cannot shrink yet.  A learner on a
+        DeviceData: store.remove(ids) followed by sync_data(); other learners on the store go on on the rows they know until
+        they call sync_data() themselves."""
+        from .device_data import normalize_ids, removal_map
+        if self.world > 1:
+            raise NotImplementedError("row sharding cannot shrink yet: remove_data() needs all rows on one rank")
+        n = self._num_samples()
+        if isinstance(self.data, DeviceData):
+            self.data.remove(ids)
+            self.sync_data()
+            return self.last_index_map if self.last_index_map is not None else np.arange(n, dtype=np.int64)
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if i >= n:
+                raise ValueError("%d is a query row or outside the %d samples: it cannot be removed" % (i, n))
+        removed = normalize_ids(ids, n)
+        if not removed:
+            return np.arange(n, dtype=np.int64)
+        self.gp.drop_rows(removed)
+        self.data = self.gp.X_host
+        self._ids_after_removal(removed)
+        self._fitted = self.gp.m > 0
+        self._start_afresh()
+        return removal_map(n, removed)
 
     #: attributes that hold buffers or caches of one learner's last fetch: a clone starts without them
     _FETCH_STATE = ("_unseen", "_last_batch", "_fetch_bufs", "_round_bufs", "_block_bufs", "_gram_bufs", "_err_bufs",
