@@ -250,6 +250,23 @@ EVIDENCE_SIGNATURES = {
 }
 
 
+class ItalEvidenceGradDesc(ctypes.Structure):
+    """ital_evidence_grad_desc (include/ital_evidence_grad.h): the labelled set, a chunk of candidates and where their log
+    marginal likelihoods and gradients go."""
+    _fields_ = [("XT", c_void_p), ("XTn", c_void_p), ("ldx", c_int), ("y", c_void_p), ("m", c_int), ("params", c_void_p),
+                ("G", c_int), ("K", c_void_p), ("ld", c_int64), ("values", c_void_p), ("grad", c_void_p), ("info", c_void_p),
+                ("status", c_void_p), ("work", c_void_p), ("work_doubles", c_int64), ("ev", c_void_p)]
+
+
+#: GP evidence with its gradient in the log-parameters, declared in include/ital_evidence_grad.h
+EVIDENCE_GRAD_SIGNATURES = {
+    "ital_sqdist_lower": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "ital_chol_gram_inverse_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ital_gp_evidence_grad": (c_int, [ctypes.POINTER(ItalEvidenceGradDesc), c_void_p]),
+    "ital_gp_evidence_grad_workspace": (c_int64, [c_int, c_int]),
+}
+
+
 #: element types of ital_ingest_rows (include/ital_ingest.h)
 INGEST_F64, INGEST_F32, INGEST_F16, INGEST_BF16 = 0, 1, 2, 3
 
@@ -306,7 +323,7 @@ def load(path=LIB_PATH):
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-            list(COMPACT_SIGNATURES.items()):
+            list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

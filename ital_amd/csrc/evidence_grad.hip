@@ -1,0 +1,398 @@
+// The log marginal likelihood of G hyper-parameter candidates and its gradient in (log l, log var, log noise), for fitting a
+// live session's kernel by gradient ascent (include/ital_evidence_grad.h; GaussianProcess.evidence_grad, tune.maximize_lml,
+// ActiveRetrievalBase.fit_params).
+//
+//   ital_sqdist_lower               the squared distances every candidate shares, with the bits ital_gram_grid forms
+//   ital_chol_gram_inverse_batched  W = M^T M, the lower triangle of K^-1, from the inverse factors M = L^-1
+//   ital_gp_evidence_grad           setup, ital_gram_grid, ital_chol_batched, ital_chol_solve_batched,
+//                                   ital_chol_inv_diag_batched, squared distances, fused product, reduction
+//
+// The five leading stages are the entry points ital_gp_evidence runs, with the same arguments: factor, alpha and inverse
+// diagonal have its bits, and the reduction restates its two serial sums, so lml has them too.  The product is the 128 x 128
+// LDS-staged v_mfma_f64_16x16x4_f64 tile of mfma_tile.h (its LDS layout and mfma_stage) with BOTH operands read k-major
+// behind predicates (tile_tn below): M is stored [k][i], W_ij = sum_k M[k][i] M[k][j] runs down its columns, and a run of 16
+// neighbouring columns of one row k is one 128-byte read.  In the chain W never reaches memory: the epilogue turns a tile
+// into two numbers.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "ital_evidence_grad.h"
+#include "ital_internal.h"
+#include "mfma_tile.h"
+
+namespace ital {
+namespace evidence_grad {
+
+using namespace ital::tile;
+
+// ------------------------------------------------------------------------------------------------- squared distances
+struct DistArgs {
+    const double* XT; const double* xn; int m; int ldx;
+    double* D; int64_t ld;
+};
+
+// grid: lower tile pairs.  gram_grid_kernel up to its candidate loop: the same operands, tile and expression.
+__global__ __launch_bounds__(256, 2) void sqdist_lower_kernel(DistArgs a) {
+    __shared__ StageLds lds;
+    const int64_t m = a.m;
+    int ti, tj;
+    tri_pair(blockIdx.x, ti, tj);
+    const int64_t i0 = (int64_t)ti * T, j0 = (int64_t)tj * T;
+    if (i0 >= m) return;
+    int sk, srow;
+    stage_role(sk, srow);
+    const double* pa[4];
+    const double* pb[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {     // rows past m: the last row (computed, never stored)
+        pa[u] = a.XT + min(i0 + srow + 8 * u, m - 1) * a.ldx + sk;
+        pb[u] = a.XT + min(j0 + srow + 8 * u, m - 1) * a.ldx + sk;
+    }
+    d4 acc[4][4];
+    zero_acc(acc);
+    tile_nt(pa, pb, a.ldx, lds, acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, kg = lane >> 4;
+    const int64_t iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int64_t j = jw + 16 * q + col;
+        const double bnj = a.xn[min(j, m - 1)];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            if (iw + 16 * p >= m || jw + 16 * q > iw + 16 * p + 15) continue;     // nothing at or below the diagonal
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int64_t i = iw + 16 * p + kg + 4 * reg;
+                const double ani = a.xn[min(i, m - 1)];
+                if (i < m && j <= i) a.D[i * a.ld + j] = rbf_sqdist(ani, bnj, acc[p][q][reg]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- W = M^T M
+// acc[p][q] += sum over kbeg <= k < kend of A(k, r) B(k, c) for the 128 x 128 tile of a workgroup of 256 threads: wave
+// (wy, wx) owns tile rows 64 wy + 16 p + (kg + 4 reg) and tile columns 64 wx + 16 q + col (D layout of the f64 MFMA).
+// fa(k, r) / fb(k, c): the element of A at tile row r / of B at tile column c, both k-major; they return 0 outside their
+// operand (k at or past kend included).  Thread (k = tid / 16, tid % 16) stages eight runs of 16 columns of its k for each
+// operand, into the layout mfma_stage reads.  Register + LDS double buffer, one barrier per stage; ends with a barrier.
+template <class FA, class FB>
+__device__ inline void tile_tn(FA fa, FB fb, int kbeg, int kend, StageLds& lds, d4 acc[4][4]) {
+    const int kb = threadIdx.x >> 4, c16 = threadIdx.x & 15;
+    double ra[8], rb[8];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            ra[u] = fa(k0 + kb, c16 + 16 * u);
+            rb[u] = fb(k0 + kb, c16 + 16 * u);
+        }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            lds[buf][0][kb][c16 + 16 * u] = ra[u];
+            lds[buf][1][kb][c16 + 16 * u] = rb[u];
+        }
+    };
+    const int nstep = (kend - kbeg + KS - 1) / KS;
+    if (nstep <= 0) return;
+    fetch(kbeg);
+    stage(0);
+    __syncthreads();
+    for (int s_ = 0; s_ < nstep; s_++) {
+        const int buf = s_ & 1;
+        if (s_ + 1 < nstep) fetch(kbeg + (s_ + 1) * KS);
+        mfma_stage(lds, buf, acc);
+        if (s_ + 1 < nstep) stage(buf ^ 1);
+        __syncthreads();
+    }
+}
+
+struct ProdArgs {
+    const double* M; int n; const int* info;       // inverse factor g at M + g n n, row stride n, lower triangle
+    double* W; int64_t ldw;                        // stored form: W_g at W + g n ldw
+    const double* D; int64_t ldd;                  // fused form: the shared squared distances,
+    const double* alpha;                           //   alpha_g at alpha + g n,
+    const double* params;                          //   [G][3],
+    double* part;                                  //   out [G][pairs][2]: sum of t, sum of t D over the tile pair's lower elements
+};
+
+// grid: (lower tile pairs, matrices).  Tile (ti, tj), ti >= tj, of W_g = M_g^T M_g: k runs from the tile's first row (M is
+// lower triangular: M[k][i] = 0 for k < i) to n; the predicates i <= k, j <= k keep every read inside the lower triangle.
+// FUSED: t_ij = (alpha_i alpha_j - W_ij) var exp(D_ij / (-2 l^2)), counted twice below the diagonal, and t_ij D_ij are
+// summed per lane (q, p, reg ascending), then over the workgroup by a fixed binary tree in LDS.
+template <bool FUSED>
+__global__ __launch_bounds__(256, 2) void gram_inverse_kernel(ProdArgs a) {
+    __shared__ StageLds lds;
+    const int g = blockIdx.y, n = a.n;
+    const bool skip = a.info && a.info[g] != 0;
+    if (FUSED && skip) return;
+    int ti, tj;
+    tri_pair(blockIdx.x, ti, tj);
+    const int i0 = ti * T, j0 = tj * T;
+    if (i0 >= n) return;
+    const double* M = a.M + (int64_t)g * n * n;
+    d4 acc[4][4];
+    zero_acc(acc);
+    if (!skip) {
+        auto fa = [&](int k, int r) {
+            const int i = i0 + r;
+            return (k < n && i <= k) ? M[(int64_t)k * n + i] : 0.0;
+        };
+        auto fb = [&](int k, int c) {
+            const int j = j0 + c;
+            return (k < n && j <= k) ? M[(int64_t)k * n + j] : 0.0;
+        };
+        tile_tn(fa, fb, i0, n, lds, acc);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane & 15, kg = lane >> 4;
+    const int iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
+    if (!FUSED) {
+        double* W = a.W + (int64_t)g * n * a.ldw;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int j = jw + 16 * q + col;
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                if (iw + 16 * p >= n || jw + 16 * q > iw + 16 * p + 15) continue;
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    const int i = iw + 16 * p + kg + 4 * reg;
+                    if (i < n && j <= i) W[(int64_t)i * a.ldw + j] = skip ? __builtin_nan("") : acc[p][q][reg];
+                }
+            }
+        }
+        return;
+    }
+    const double l = a.params[3 * (int64_t)g], var = a.params[3 * (int64_t)g + 1];
+    const double s = -2.0 * l * l;
+    const double* alpha = a.alpha + (int64_t)g * n;
+    double sv = 0.0, sd = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int j = jw + 16 * q + col;
+        const double aj = alpha[min(j, n - 1)];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            if (iw + 16 * p >= n || jw + 16 * q > iw + 16 * p + 15) continue;
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int i = iw + 16 * p + kg + 4 * reg;
+                if (i < n && j <= i) {
+                    const double d = a.D[(int64_t)i * a.ldd + j];
+                    double t = (alpha[i] * aj - acc[p][q][reg]) * (var * exp(d / s));
+                    if (j < i) t += t;
+                    sv += t;
+                    sd += t * d;
+                }
+            }
+        }
+    }
+    double (*red)[256] = (double (*)[256]) & lds[0][0][0][0];     // tile_tn ended with a barrier: the stage buffers are free
+    const int tid = threadIdx.x;
+    red[0][tid] = sv;
+    red[1][tid] = sd;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) {
+            red[0][tid] += red[0][tid + h];
+            red[1][tid] += red[1][tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid < 2) a.part[((int64_t)g * gridDim.x + blockIdx.x) * 2 + tid] = red[tid][0];
+}
+
+// --------------------------------------------------------------------------------------------- setup and the reduction
+struct Layout {          // of the workspace of ital_gp_evidence_grad, in doubles from its start
+    int64_t alpha, cdiag, M, Kp, yp, ldv, nv, D, part, pairs, total;
+};
+
+__host__ __device__ inline Layout layout(int64_t m, int64_t G) {
+    Layout w;
+    const int64_t tn = (m + T - 1) / T;
+    w.pairs = tn * (tn + 1) / 2;
+    w.alpha = 0;
+    w.cdiag = w.alpha + G * m;
+    w.M = w.cdiag + G * m;          // ital_chol_inv_diag_batched's workspace
+    w.Kp = w.M + G * m * m;
+    w.yp = w.Kp + G;
+    w.ldv = w.yp + G;
+    w.nv = w.ldv + G;               // n as int: half of it used
+    w.D = w.nv + G;                 // [m][m], shared by the candidates
+    w.part = w.D + m * m;
+    w.total = w.part + G * w.pairs * 2;
+    return w;
+}
+
+struct GradArgs {
+    const double* y; int m; int G;
+    const double* params;
+    double* K; int64_t ld;
+    double* values; double* grad; const int* info;
+    double* work;
+};
+
+// Workgroup g: the entries of the batched calls' argument arrays for candidate g, and y as the solve's right-hand side.
+__global__ __launch_bounds__(256) void grad_setup_kernel(GradArgs a) {
+    const int g = blockIdx.x;
+    const Layout w = layout(a.m, a.G);
+    double* alpha = a.work + w.alpha + (int64_t)g * a.m;
+    if (threadIdx.x == 0) {
+        ((double**)(a.work + w.Kp))[g] = a.K + (int64_t)g * a.m * a.ld;
+        ((double**)(a.work + w.yp))[g] = alpha;
+        ((int64_t*)(a.work + w.ldv))[g] = a.ld;
+        ((int*)(a.work + w.nv))[g] = a.m;
+    }
+    for (int i = threadIdx.x; i < a.m; i += 256) alpha[i] = a.y[i];
+}
+
+// Workgroup g: lml and the three gradient components of candidate g.  The terms of 256 samples at a time are formed by all
+// threads, then four threads add one kind each, i ascending -- y.alpha and sum log L_ii as evidence_reduce_kernel adds them
+// (the same terms, order and closing expression: the same bits), alpha.alpha and sum c_i likewise.  Thread 4 adds the tile
+// pairs' partials in ascending tile order.
+__global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs a) {
+    __shared__ double term[4][256];
+    __shared__ double tot[6];
+    const int g = blockIdx.x, m = a.m, tid = threadIdx.x;
+    double* gr = a.grad + 3 * (int64_t)g;
+    if (a.info[g] != 0) {
+        if (tid == 0) a.values[g] = -__builtin_inf();
+        if (tid < 3) gr[tid] = __builtin_nan("");
+        return;
+    }
+    const Layout w = layout(m, a.G);
+    const double* alpha = a.work + w.alpha + (int64_t)g * m;
+    const double* cd = a.work + w.cdiag + (int64_t)g * m;
+    const double* L = a.K + (int64_t)g * m * a.ld;
+    const double log2pi = 1.8378770664093454836;
+    double sum = 0.0;          // threads 0..3: y.alpha, sum log L_ii, alpha.alpha, sum c_i
+    for (int i0 = 0; i0 < m; i0 += 256) {
+        const int i = i0 + tid;
+        if (i < m) {
+            const double yi = a.y[i], al = alpha[i];
+            term[0][tid] = yi * al;
+            term[1][tid] = log(L[(int64_t)i * a.ld + i]);
+            term[2][tid] = al * al;
+            term[3][tid] = cd[i];
+        }
+        __syncthreads();
+        if (tid < 4) {
+            const int cnt = min(256, m - i0);
+            for (int e = 0; e < cnt; e++) sum += term[tid][e];
+        }
+        __syncthreads();
+    }
+    if (tid == 4) {
+        const double* part = a.work + w.part + (int64_t)g * w.pairs * 2;
+        double sv = 0.0, sd = 0.0;
+        for (int64_t t = 0; t < w.pairs; t++) {
+            sv += part[2 * t];
+            sd += part[2 * t + 1];
+        }
+        tot[4] = sv;
+        tot[5] = sd;
+    }
+    if (tid == 0) term[0][0] = sum;
+    if (tid == 1) term[1][0] = sum;
+    if (tid == 2) tot[2] = sum;
+    if (tid == 3) tot[3] = sum;
+    __syncthreads();
+    if (tid == 0) a.values[g] = -0.5 * term[0][0] - term[1][0] - 0.5 * (double)m * log2pi;
+    if (tid == 1) {
+        const double l = a.params[3 * (int64_t)g], noise = a.params[3 * (int64_t)g + 2];
+        gr[0] = 0.5 * tot[5] / (l * l);
+        gr[1] = 0.5 * tot[4];
+        gr[2] = 0.5 * noise * (tot[2] - tot[3]);
+    }
+}
+
+}  // namespace evidence_grad
+}  // namespace ital
+
+using namespace ital::evidence_grad;
+
+static int launch_sqdist(const double* XT, const double* XTn, int m, int ldx, double* D, int64_t ld, hipStream_t stream) {
+    const int64_t tn = ((int64_t)m + T - 1) / T, pairs = tn * (tn + 1) / 2;
+    DistArgs a = {XT, XTn, m, ldx, D, ld};
+    ITAL_LAUNCH(sqdist_lower_kernel, dim3((unsigned)pairs), dim3(256), 0, stream, a);
+    return ital_check_launch("ital_sqdist_lower");
+}
+
+extern "C" int ital_sqdist_lower(const double* XT, const double* XTn, int m, int ldx, double* D, int64_t ld,
+                                 hipStream_t stream) {
+    if (!XT || !XTn || !D) return ital_fail(-22, "ital_sqdist_lower: NULL pointer");
+    if (m < 1) return ital_fail(-22, "ital_sqdist_lower: m must be at least 1");
+    if (ldx <= 0 || ldx % 16 != 0) return ital_fail(-22, "ital_sqdist_lower: ldx must be a positive multiple of 16");
+    if (ld < m) return ital_fail(-22, "ital_sqdist_lower: ld must be at least m");
+    if (m > (1 << 22)) return ital_fail(-22, "ital_sqdist_lower: matrix too large");
+    return launch_sqdist(XT, XTn, m, ldx, D, ld, stream);
+}
+
+extern "C" int ital_chol_gram_inverse_batched(const double* M, int n, int count, const int* info, double* W, int64_t ldw,
+                                              hipStream_t stream) {
+    if (!M || !W) return ital_fail(-22, "ital_chol_gram_inverse_batched: NULL pointer");
+    if (n < 1 || count < 1) return ital_fail(-22, "ital_chol_gram_inverse_batched: n and count must be at least 1");
+    if (count > 65535) return ital_fail(-22, "ital_chol_gram_inverse_batched: more than 65535 matrices per call");
+    if (ldw < n) return ital_fail(-22, "ital_chol_gram_inverse_batched: ldw must be at least n");
+    if (n > (1 << 22)) return ital_fail(-22, "ital_chol_gram_inverse_batched: matrix too large");
+    const int64_t tn = ((int64_t)n + T - 1) / T, pairs = tn * (tn + 1) / 2;
+    ProdArgs a = {M, n, info, W, ldw, nullptr, 0, nullptr, nullptr, nullptr};
+    ITAL_LAUNCH(gram_inverse_kernel<false>, dim3((unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
+    return ital_check_launch("ital_chol_gram_inverse_batched");
+}
+
+extern "C" int64_t ital_gp_evidence_grad_workspace(int m, int G) {
+    if (m < 1 || G < 1) return 0;
+    return layout(m, G).total;
+}
+
+extern "C" int ital_gp_evidence_grad(const ital_evidence_grad_desc* d, hipStream_t stream) {
+    if (!d) return ital_fail(-22, "ital_gp_evidence_grad: NULL descriptor");
+    if (!d->XT || !d->XTn || !d->y || !d->params || !d->K || !d->values || !d->grad || !d->info || !d->status || !d->work)
+        return ital_fail(-22, "ital_gp_evidence_grad: NULL pointer");
+    if (d->m < 1 || d->G < 1) return ital_fail(-22, "ital_gp_evidence_grad: m and G must be at least 1");
+    if (d->G > 65535) return ital_fail(-22, "ital_gp_evidence_grad: more than 65535 candidates per call");
+    if (d->m > (1 << 22)) return ital_fail(-22, "ital_gp_evidence_grad: matrix too large");
+    if (d->ldx <= 0 || d->ldx % 16 != 0) return ital_fail(-22, "ital_gp_evidence_grad: ldx must be a positive multiple of 16");
+    if (d->ld < d->m) return ital_fail(-22, "ital_gp_evidence_grad: ld must be at least m");
+    const Layout w = layout(d->m, d->G);
+    if (d->work_doubles < w.total)
+        return ital_fail(-22, "ital_gp_evidence_grad: work smaller than ital_gp_evidence_grad_workspace(m, G)");
+    const int m = d->m, G = d->G;
+    auto mark = [&](int k) {
+        return (d->ev && hipEventRecord((hipEvent_t)d->ev[k], stream) != hipSuccess)
+                   ? ital_fail(-5, "ital_gp_evidence_grad: hipEventRecord failed") : 0;
+    };
+    double* const* Kp = (double* const*)(d->work + w.Kp);
+    double* const* yp = (double* const*)(d->work + w.yp);
+    const int64_t* ldv = (const int64_t*)(d->work + w.ldv);
+    const int* nv = (const int*)(d->work + w.nv);
+    GradArgs a = {d->y, m, G, d->params, d->K, d->ld, d->values, d->grad, d->info, d->work};
+    int rc;
+    ITAL_LAUNCH(grad_setup_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
+    if ((rc = ital_check_launch("ital_gp_evidence_grad(setup)"))) return rc;
+    if ((rc = mark(0))) return rc;
+    if ((rc = ital_gram_grid(d->XT, d->XTn, m, d->ldx, d->params, G, d->K, d->ld, stream))) return rc;
+    if ((rc = mark(1))) return rc;
+    if ((rc = ital_chol_batched(Kp, nv, ldv, G, m, d->info, d->status, stream))) return rc;
+    if ((rc = mark(2))) return rc;
+    if ((rc = ital_chol_solve_batched(Kp, nv, ldv, yp, G, d->info, stream))) return rc;
+    if ((rc = mark(3))) return rc;
+    if ((rc = ital_chol_inv_diag_batched(Kp, ldv, m, G, d->info, d->work + w.cdiag, m, d->work + w.M, (int64_t)G * m * m,
+                                         stream)))
+        return rc;
+    if ((rc = mark(4))) return rc;
+    if ((rc = launch_sqdist(d->XT, d->XTn, m, d->ldx, d->work + w.D, m, stream))) return rc;
+    if ((rc = mark(5))) return rc;
+    ProdArgs p = {d->work + w.M, m, d->info, nullptr, 0, d->work + w.D, m, d->work + w.alpha, d->params, d->work + w.part};
+    ITAL_LAUNCH(gram_inverse_kernel<true>, dim3((unsigned)w.pairs, (unsigned)G), dim3(256), 0, stream, p);
+    if ((rc = ital_check_launch("ital_gp_evidence_grad(product)"))) return rc;
+    if ((rc = mark(6))) return rc;
+    ITAL_LAUNCH(grad_reduce_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
+    if ((rc = ital_check_launch("ital_gp_evidence_grad(reduction)"))) return rc;
+    return mark(7);
+}

@@ -777,6 +777,76 @@ class GaussianProcess(object):
                 out["loo_var"][g0:g0 + c] = lv[:c].cpu().numpy()
         return out
 
+    def evidence_grad_chunk(self, max_bytes=1 << 30):
+        """Candidates evidence_grad() sends to the device at once so that their Grams, workspace and outputs stay below
+        `max_bytes` (at most 65535, the limit of one ital_gp_evidence_grad call); MemoryError if one candidate alone exceeds
+        it.  The squared distances are shared by the candidates of a chunk and counted once."""
+        m = self.m
+        one, two = (int(self._lib.ital_gp_evidence_grad_workspace(m, c)) for c in (1, 2))
+        per = 8 * (m * m + (two - one) + 5)
+        shared = 8 * (2 * one - two)
+        if shared + per > max_bytes:
+            raise MemoryError("one candidate at m = %d takes %d bytes, more than max_bytes = %d" % (m, shared + per, max_bytes))
+        return int(min((max_bytes - shared) // per, 65535))
+
+    def evidence_grad(self, params_list, *, max_bytes=1 << 30, events=None):
+        """The log marginal likelihood of hyper-parameter candidates on the model's own labelled set (queries included) and
+        its gradient in the LOGARITHMS of the parameters, without touching the model: for each dict of `params_list`
+        (`length_scale`, optional `var` / `noise`; default: the model's current value) the quantities of
+        include/ital_evidence_grad.h.  Returns a dict of numpy arrays: `lml` [G] (the bits evidence() returns), `grad`
+        [G, 3] (d lml / d log length_scale, d log var, d log noise), `ok` [G] bool (the candidate's Gram was positive
+        definite; otherwise -inf and a NaN row).
+
+        Argument handling, chunking and errors are those of evidence(): chunks whose Grams and workspace stay below
+        `max_bytes`, values that do not depend on the chunking; XT, XTn and y are read and only buffers of the call's own are
+        written -- L, alpha, V, mu, s2, the status word and both random streams stay as they are.  Every rank computes the same
+        thing locally: no collective.  RuntimeError for an unfitted model, ValueError for a non-positive length_scale / var,
+        MemoryError if one candidate alone exceeds max_bytes.
+        `events`: None, or eight recorded torch events that bracket the seven stages of the LAST chunk
+        (tools/evidence_grad_bench.py)."""
+        if self.m == 0:
+            raise RuntimeError("the GP has not been fitted")
+        prm = np.empty((len(params_list), 3), dtype=np.float64)
+        for g, p in enumerate(params_list):
+            unknown = set(p) - {"length_scale", "var", "noise"}
+            if unknown:
+                raise TypeError("unexpected GP parameters: %s" % ", ".join(sorted(unknown)))
+            prm[g] = (float(p.get("length_scale", self.length_scale)), float(p.get("var", self.var)),
+                      float(p.get("noise", self.noise)))
+            if not (prm[g, 0] > 0 and prm[g, 1] > 0):
+                raise ValueError("length_scale and var must be positive")
+        G, m, lib, dev = len(prm), self.m, self._lib, self.device
+        out = dict(lml=np.empty(G), grad=np.empty((G, 3)), ok=np.zeros(G, dtype=bool))
+        if G == 0:
+            return out
+        chunk = min(G, self.evidence_grad_chunk(max_bytes))
+        with torch.cuda.device(dev):
+            yd = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(dev)
+            pd = torch.from_numpy(prm).to(dev)
+            K = torch.empty(chunk * m * m, dtype=torch.float64, device=dev)
+            need = int(lib.ital_gp_evidence_grad_workspace(m, chunk))
+            work = torch.empty(need, dtype=torch.float64, device=dev)
+            values = torch.empty(chunk, dtype=torch.float64, device=dev)
+            grad = torch.empty((chunk, 3), dtype=torch.float64, device=dev)
+            info = torch.empty(chunk, dtype=torch.int32, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)      # the call's own word: the model's is not touched
+            d = _lib.ItalEvidenceGradDesc()
+            d.XT, d.XTn, d.ldx, d.y, d.m = _ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(yd), m
+            d.K, d.ld, d.values, d.grad, d.info = _ptr(K), m, _ptr(values), _ptr(grad), _ptr(info)
+            d.status, d.work, d.work_doubles = _ptr(status), _ptr(work), need
+            for g0 in range(0, G, chunk):
+                c = min(chunk, G - g0)
+                d.params, d.G = pd.data_ptr() + 24 * g0, c
+                ev = None
+                if events is not None and g0 + c == G:
+                    ev = (ctypes.c_void_p * 8)(*[e.cuda_event for e in events])
+                d.ev = ctypes.addressof(ev) if ev is not None else None
+                check(lib.ital_gp_evidence_grad(ctypes.byref(d), _stream()))
+                out["lml"][g0:g0 + c] = values[:c].cpu().numpy()      # synchronises: the chunk's buffers are free again
+                out["grad"][g0:g0 + c] = grad[:c].cpu().numpy()
+                out["ok"][g0:g0 + c] = info[:c].cpu().numpy() == 0
+        return out
+
     def check_status(self, status=None):
         """Raises if a kernel flagged a numerical failure.  `status`: the word as already downloaded (e.g. the OR over all
         ranks that the selection step returns); otherwise this rank's word is read (synchronises).  Bit 1 comes from the

@@ -401,6 +401,212 @@ def optimize_session_params(gp_or_learner, grid=default_grids['ls_only'], init=N
     return _alternating_search(grid, init, lambda cv_list: session_scores(gp_or_learner, cv_list, criterion), verbose)
 
 
+# ------------------------------------------------------------------ a live session, continuously: evidence gradients
+PARAM_NAMES = ('length_scale', 'var', 'noise')
+
+#: the box fit_session_params searches by default: the span of default_grids['full'] in length scale and variance, and a
+#: noise between the grid's floor, 1e-8 (strictly positive: the factor's pivots stay away from 0), and the variance's scale
+DEFAULT_FIT_BOUNDS = {'length_scale': (1e-3, 25.0), 'var': (0.1, 10.0), 'noise': (1e-8, 1.0)}
+
+
+#: L-BFGS-B's stopping rules in maximize_lml.  The objective is a SUM over restarts: scipy's default relative decrease
+#: (ftol 2.2e-9) of the sum would stop the run while single restarts still climb, so both rules are set near machine precision
+#: and `maxiter` is what ends a run that keeps creeping.
+LBFGSB_OPTIONS = dict(maxcor=10, ftol=1e-15, gtol=1e-9, maxls=30)
+
+
+class _Dropped(Exception):
+    """An evaluation inside scipy's iteration came back with restarts that are not positive definite."""
+
+    def __init__(self, bad):
+        Exception.__init__(self)
+        self.bad = bad
+
+
+def _bounds_array(bounds):
+    b = dict(DEFAULT_FIT_BOUNDS)
+    b.update(bounds or {})
+    unknown = set(b) - set(PARAM_NAMES)
+    if unknown:
+        raise TypeError('unexpected GP parameters: %s' % ', '.join(sorted(unknown)))
+    arr = np.array([[float(b[k][0]), float(b[k][1])] for k in PARAM_NAMES])
+    if not np.all((arr[:, 0] > 0) & (arr[:, 0] <= arr[:, 1])):
+        raise ValueError('bounds must satisfy 0 < low <= high')
+    return arr
+
+
+def _free_columns(free):
+    free = tuple(free)
+    unknown = set(free) - set(PARAM_NAMES)
+    if unknown:
+        raise TypeError('unexpected GP parameters: %s' % ', '.join(sorted(unknown)))
+    cols = [k for k, name in enumerate(PARAM_NAMES) if name in free]
+    if not cols:
+        raise ValueError('no parameter to fit')
+    return cols
+
+
+def maximize_lml(evaluate, starts, bounds=None, free=PARAM_NAMES, maxiter=100):
+    """Maximises a log marginal likelihood over the logarithms of (length_scale, var, noise) from R starting points at once
+    (host only: `evaluate` is all it knows of the model).
+
+    `evaluate(theta[R', 3]) -> (lml[R'], grad[R', 3], ok[R'])`: values and gradients in (log length_scale, log var,
+    log noise) of a batch of parameter triples -- GaussianProcess.evidence_grad behind fit_session_params.  `starts`: [R, 3]
+    triples; `bounds`: dict name -> (low, high), defaults DEFAULT_FIT_BOUNDS (starts are clipped into them); `free`: the
+    names that move.  The other columns keep their start values bit for bit, and their gradient components are ignored.
+
+    One scipy.optimize.minimize(method='L-BFGS-B', jac=True) runs over the concatenated free log-parameters of all restarts
+    with the objective -sum_r lml_r.  The sum is separable, so its gradient is the restarts' own gradients side by side and
+    every restart climbs its own hill, while one call of `evaluate` serves all of them per iteration.  A restart whose
+    evaluation comes back ok = False (its Gram is not positive definite there) is dropped, and the survivors resume from the
+    last iterate, with what is left of `maxiter`.  Because the line search accepts a step on the SUM, a single restart may
+    lose a little in a step that the others gain from: each restart therefore reports the best point at which it was
+    evaluated, which is never below its start.
+
+    Returns (best, lml, records): `best` a dict of all three parameters at the best restart (None and -inf if no restart is
+    left), `records` one dict per start -- `start`, `params`, `lml` (its best evaluation), `dropped`, and the `iterations`
+    and `evaluations` of the run it was part of."""
+    from scipy.optimize import minimize
+    cols = _free_columns(free)
+    box = _bounds_array(bounds)
+    starts = np.array(starts, dtype=np.float64).reshape(-1, 3)
+    R, nf = len(starts), len(cols)
+    start_theta = starts.copy()
+    start_theta[:, cols] = np.clip(starts[:, cols], box[cols, 0], box[cols, 1])
+    x_start = np.log(start_theta[:, cols])
+    best_lml = np.full(R, -np.inf)
+    best_theta = start_theta.copy()
+    dropped = np.zeros(R, dtype=bool)
+    alive = np.arange(R)
+    x_cur = x_start.copy()                      # [R, nf]: the last iterate of every restart
+    evaluations, iterations = 0, 0
+
+    def theta_of(x, rows):
+        theta = start_theta[rows].copy()
+        exact = x == x_start[rows]             # a point that has not moved is its start, not exp(log(start))
+        theta[:, cols] = np.where(exact, start_theta[rows][:, cols], np.exp(x))
+        return theta
+
+    while len(alive) and iterations < max(1, maxiter):
+        rows = alive
+
+        def objective(xflat):
+            nonlocal evaluations
+            x = xflat.reshape(len(rows), nf)
+            theta = theta_of(x, rows)
+            lml, grad, ok = evaluate(theta)
+            evaluations += 1
+            lml, grad = np.asarray(lml, dtype=np.float64), np.asarray(grad, dtype=np.float64).reshape(len(rows), 3)
+            ok = np.asarray(ok, dtype=bool) & np.isfinite(lml) & np.all(np.isfinite(grad[:, cols]), axis=1)
+            better = ok & (lml > best_lml[rows])
+            best_lml[rows[better]] = lml[better]
+            best_theta[rows[better]] = theta[better]
+            if not ok.all():
+                raise _Dropped(~ok)
+            return -float(lml.sum()), -grad[:, cols].reshape(-1)
+
+        def callback(xk):
+            nonlocal iterations
+            iterations += 1
+            x_cur[rows] = xk.reshape(len(rows), nf)
+
+        try:
+            minimize(objective, x_cur[rows].reshape(-1), jac=True, method='L-BFGS-B',
+                     bounds=[tuple(np.log(box[c])) for _ in rows for c in cols], callback=callback,
+                     options=dict(LBFGSB_OPTIONS, maxiter=max(1, maxiter - iterations)))
+            break
+        except _Dropped as e:
+            dropped[rows[e.bad]] = True
+            alive = rows[~e.bad]
+
+    records = [dict(start=dict(zip(PARAM_NAMES, (float(v) for v in starts[r]))),
+                    params=dict(zip(PARAM_NAMES, (float(v) for v in best_theta[r]))) if np.isfinite(best_lml[r]) else None,
+                    lml=float(best_lml[r]), dropped=bool(dropped[r]), iterations=iterations, evaluations=evaluations)
+               for r in range(R)]
+    best_lml = np.where(dropped, -np.inf, best_lml)          # the result comes from the survivors
+    if not np.any(np.isfinite(best_lml)):
+        return None, -np.inf, records
+    r = int(np.argmax(best_lml))
+    return records[r]['params'], float(best_lml[r]), records
+
+
+def session_starts(init, restarts=8, bounds=None, free=PARAM_NAMES):
+    """The starting points of fit_session_params, [R, 3] rows of (length_scale, var, noise), R <= restarts.  Row 0 is `init`.
+    The others are a fixed design inside the box -- no random generator is involved: n_l length scales crossed with n_n
+    noise levels, length scale varying fastest, of which the first restarts - 1 are taken; n_n = 2 when at least four
+    points are wanted, else 1, and n_l = ceil((restarts - 1) / n_n).  Both sets are log-spaced and strictly inside their
+    bounds, low (high / low)^(k / (n + 1)), k = 1 .. n.  `var` starts at init's value everywhere, and so does a parameter
+    that is not in `free` (the design then collapses along it; duplicate rows are left out)."""
+    cols = _free_columns(free)
+    box = _bounds_array(bounds)
+    init = np.array([float(init[k]) for k in PARAM_NAMES])
+    rows = [init]
+    want = max(0, int(restarts) - 1)
+    if want:
+        n_n = 2 if (want >= 4 and 2 in cols and 0 in cols) else 1
+        n_l = -(-want // n_n)
+        inside = lambda lo, hi, n: [lo * (hi / lo) ** (k / (n + 1.0)) for k in range(1, n + 1)]
+        ls = inside(box[0, 0], box[0, 1], n_l) if 0 in cols else [init[0]]
+        if 2 in cols:
+            ns = inside(box[2, 0], box[2, 1], n_n if 0 in cols else want)
+        else:
+            ns = [init[2]]
+        for noise in ns:
+            for l in ls:
+                row = np.array([l, init[1], noise])
+                if len(rows) <= want and not any(np.array_equal(row, r) for r in rows):
+                    rows.append(row)
+    return np.array(rows)
+
+
+def fit_session_params(gp_or_learner, params=PARAM_NAMES, init=None, restarts=8, bounds=None, maxiter=100, verbose=0,
+                       records=None):
+    """Fits kernel hyper-parameters of a live session -- a GaussianProcess or a learner -- to its own labels by maximising the
+    log marginal likelihood continuously, from its gradient on the device (GaussianProcess.evidence_grad,
+    include/ital_evidence_grad.h): what GaussianProcessRegressor.fit does, and the other half of optimize_session_params,
+    which can only find what lies on its grid.
+
+    `params`: the names that are fitted; the others stay at `init`.  `init`: dict of starting values (None, or a missing
+    name: the session's current value); it is restart 0.  The other restarts are the fixed design of session_starts inside
+    `bounds` (dict name -> (low, high); what is missing comes from DEFAULT_FIT_BOUNDS, whose noise floor is 1e-8); all of
+    them run in one L-BFGS-B iteration (maximize_lml), one device call per evaluation.  No random generator is touched.
+    `verbose`: 1 prints the result, 2 every restart.  `records`: a list that receives maximize_lml's per-restart records.
+    Returns (dict of the fitted values of `params`, their lml) -- what set_params() takes -- or (None, -inf) if no start has
+    a positive definite Gram."""
+    gp = _session_gp(gp_or_learner)
+    cols = _free_columns(params)
+    start = {'length_scale': gp.length_scale, 'var': gp.var, 'noise': gp.noise}
+    unknown = set(init or {}) - set(PARAM_NAMES)
+    if unknown:
+        raise TypeError('unexpected GP parameters: %s' % ', '.join(sorted(unknown)))
+    start.update(init or {})
+    box = _bounds_array(bounds)
+    # restart 0 is never clipped: the box grows to hold it (a fitted parameter that starts at 0 has no logarithm: ValueError)
+    if any(not float(start[PARAM_NAMES[c]]) > 0 for c in cols):
+        raise ValueError('a fitted parameter must start at a positive value')
+    bounds = {name: (min(box[k, 0], float(start[name])), max(box[k, 1], float(start[name]))) if k in cols
+              else tuple(box[k]) for k, name in enumerate(PARAM_NAMES)}
+    starts = session_starts(start, restarts, bounds, params)
+
+    def evaluate(theta):
+        ev = gp.evidence_grad([dict(zip(PARAM_NAMES, (float(v) for v in row))) for row in theta])
+        return ev['lml'], ev['grad'], ev['ok']
+
+    best, lml, recs = maximize_lml(evaluate, starts, bounds, params, maxiter)
+    if records is not None:
+        records.extend(recs)
+    if verbose >= 2:
+        for r, rec in enumerate(recs):
+            print('restart {}: {} -> {} : {:.4f}{}'.format(r, rec['start'], rec['params'], rec['lml'],
+                                                           ' (dropped)' if rec['dropped'] else ''))
+    if best is None:
+        return None, -np.inf
+    best = {PARAM_NAMES[c]: best[PARAM_NAMES[c]] for c in cols}
+    if verbose >= 1:
+        print('{} : {:.4f}'.format(', '.join('{} = {}'.format(k, v) for k, v in best.items()), lml))
+    return best, lml
+
+
 # ------------------------------------------------------------------------------------------------------------------ CLI
 USAGE = '''
 Optimizes GP hyper-parameters for a given dataset using alternating optimization.
