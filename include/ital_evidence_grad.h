@@ -4,14 +4,16 @@
  * ActiveRetrievalBase.fit_params; csrc/evidence_grad.hip).  For candidate g with theta_g = (l, var, noise), and D, K, L,
  * alpha, c_i = (K^-1)_ii as defined in ital_evidence.h, let Kf = var exp(D / (-2 l^2)) (K without its noise) and W = K^-1:
  *
- *     lml        as ital_gp_evidence, bit for bit                                                        (R&W 2.30)
+ *     lml        as ital_gp_evidence, bit for bit: the same code forms it                                (R&W 2.30)
  *     g_logl     = 1/2 sum_ij (alpha_i alpha_j - W_ij) Kf_ij D_ij / l^2           d lml / d log l        (R&W 5.9)
  *     g_logvar   = 1/2 sum_ij (alpha_i alpha_j - W_ij) Kf_ij                      d lml / d log var
  *     g_lognoise = 1/2 noise (alpha.alpha - sum_i c_i)                            d lml / d log noise
  *
  * W = M^T M with M = L^-1, the inverse factor that ital_chol_inv_diag_batched leaves in its workspace: matrix g at
  * work + g n n, row-major [j][i] with row stride n, lower triangle (i <= j) only -- the rest of that workspace is unwritten
- * memory and is never read here.  ital_gp_evidence_grad depends on that layout.
+ * memory and is never read here.  ital_gp_evidence_grad depends on that layout, and cannot drift from it: its workspace is
+ * ital_gp_evidence's, followed by D and the partials, and its first five stages are the host function ital_gp_evidence
+ * runs (csrc/evidence_chain.h), so it reads M where that function's last launch wrote it.
  *
  * Every sum runs in a fixed order and no kernel uses atomics or lets one matrix see another: a candidate gets the same bits
  * alone or in any batch, at any position.  Conventions as in ital_evidence.h: borrowed device pointers, asynchronous on

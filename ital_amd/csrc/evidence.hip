@@ -6,6 +6,8 @@
 //   ital_chol_inv_diag_batched  (K_g^-1)_ii = sum_{j >= i} (L_g^-1)[j][i]^2 of G factors, one workgroup per matrix
 //   ital_gp_evidence            setup, Gram grid, ital_chol_batched, ital_chol_solve_batched, inverse diagonals, reduction
 //
+// All but the reduction is chain_prologue, which ital_gp_evidence_grad (evidence_grad.hip) runs too; evidence_chain.h holds
+// what the two chains share.
 // The Gram tile is the 128 x 128 LDS-staged v_mfma_f64_16x16x4_f64 tile of mfma_tile.h, the one ital_gram_rows runs on; the
 // Cholesky and the solves are dense.hip's own entry points.  Every sum has a fixed order and no kernel lets one matrix see
 // another: a candidate gets the same bits alone or in any batch.
@@ -13,14 +15,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "evidence_chain.h"
 #include "ital_evidence.h"
-#include "ital_internal.h"
-#include "mfma_tile.h"
 
 namespace ital {
 namespace evidence {
-
-using namespace ital::tile;
 
 constexpr int CH = 1024;       // columns of a factor row staged per step of the inverse-diagonal kernel
 constexpr int64_t GRID_TARGET_BLOCKS = 512;   // workgroups the Gram grid aims at: 256 CUs x 2
@@ -37,47 +36,22 @@ struct GridArgs {
 __global__ __launch_bounds__(256, 2) void gram_grid_kernel(GridArgs a) {
     __shared__ StageLds lds;
     const int64_t m = a.m;
-    int ti, tj;
-    tri_pair(blockIdx.x, ti, tj);
-    const int64_t i0 = (int64_t)ti * T, j0 = (int64_t)tj * T;
-    if (i0 >= m) return;
-    int sk, srow;
-    stage_role(sk, srow);
-    const double* pa[4];
-    const double* pb[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {     // rows past m: the last row (computed, never stored)
-        pa[u] = a.XT + min(i0 + srow + 8 * u, m - 1) * a.ldx + sk;
-        pb[u] = a.XT + min(j0 + srow + 8 * u, m - 1) * a.ldx + sk;
-    }
     d4 acc[4][4];
-    zero_acc(acc);
-    tile_nt(pa, pb, a.ldx, lds, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t iw, jw;
+    if (!sqdist_tile(a.XT, a.xn, m, a.ldx, lds, acc, iw, jw)) return;
+    const int lane = threadIdx.x & 63;
     const int col = lane & 15, kg = lane >> 4;
-    const int64_t iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
-    // D = |x_i|^2 + |x_j|^2 - 2 x_i . x_j in place (the expansion of ital_gram_rows)
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const double bnj = a.xn[min(jw + 16 * q + col, m - 1)];
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++) {
-                const double ani = a.xn[min(iw + 16 * p + kg + 4 * reg, m - 1)];
-                acc[p][q][reg] = rbf_sqdist(ani, bnj, acc[p][q][reg]);
-            }
-    }
     for (int g = blockIdx.y; g < a.G; g += gridDim.y) {
         const double l = a.params[3 * (int64_t)g], var = a.params[3 * (int64_t)g + 1], noise = a.params[3 * (int64_t)g + 2];
         const double s = -2.0 * l * l;
         double* K = a.K + (int64_t)g * m * a.ld;
+        // for_each_lower's walk, written out: through the helper exp() moves under the element test and the kernel takes
+        // 215 VGPRs instead of 214
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int64_t j = jw + 16 * q + col;
 #pragma unroll
             for (int p = 0; p < 4; p++) {
-                // a 16 x 16 sub-tile with nothing at or below the diagonal inside the matrix: the whole wave skips it
                 if (iw + 16 * p >= m || jw + 16 * q > iw + 16 * p + 15) continue;
 #pragma unroll
                 for (int reg = 0; reg < 4; reg++) {
@@ -149,32 +123,12 @@ __global__ __launch_bounds__(256) void inv_diag_batched_kernel(InvdArgs a) {
 }
 
 // --------------------------------------------------------------------------------------------- setup and the reduction
-struct Layout {          // of the workspace of ital_gp_evidence, in doubles from its start
-    int64_t alpha, cdiag, M, Kp, yp, ldv, nv, total;
-};
-
-__host__ __device__ inline Layout layout(int64_t m, int64_t G) {
-    Layout w;
-    w.alpha = 0;
-    w.cdiag = w.alpha + G * m;
-    w.M = w.cdiag + G * m;
-    w.Kp = w.M + G * m * m;
-    w.yp = w.Kp + G;
-    w.ldv = w.yp + G;
-    w.nv = w.ldv + G;
-    w.total = w.nv + G;      // n as int: half of it used
-    return w;
-}
-
-struct EvArgs {
-    const double* y; int m; int G;
-    double* K; int64_t ld;
-    double* scores; const int* info; double* loo_mean; double* loo_var; int64_t ldm;
-    double* work;
+struct SetupArgs {
+    const double* y; int m; int G; double* K; int64_t ld; double* work;
 };
 
 // Workgroup g: the entries of the batched calls' argument arrays for candidate g, and y as the solve's right-hand side.
-__global__ __launch_bounds__(256) void evidence_setup_kernel(EvArgs a) {
+__global__ __launch_bounds__(256) void chain_setup_kernel(SetupArgs a) {
     const int g = blockIdx.x;
     const Layout w = layout(a.m, a.G);
     double* alpha = a.work + w.alpha + (int64_t)g * a.m;
@@ -187,8 +141,14 @@ __global__ __launch_bounds__(256) void evidence_setup_kernel(EvArgs a) {
     for (int i = threadIdx.x; i < a.m; i += 256) alpha[i] = a.y[i];
 }
 
-// Workgroup g: loo_mean, loo_var and the four sums of candidate g.  The terms of 256 samples at a time are formed by all
-// threads, then four threads add one kind each, i ascending.
+struct EvArgs {
+    const double* y; int m; int G;
+    double* K; int64_t ld;
+    double* scores; const int* info; double* loo_mean; double* loo_var; int64_t ldm;
+    double* work;
+};
+
+// Workgroup g: loo_mean, loo_var and the four sums of candidate g (serial_sums).
 __global__ __launch_bounds__(256) void evidence_reduce_kernel(EvArgs a) {
     __shared__ double term[4][256];
     const int g = blockIdx.x, m = a.m, tid = threadIdx.x;
@@ -207,31 +167,21 @@ __global__ __launch_bounds__(256) void evidence_reduce_kernel(EvArgs a) {
     const double* alpha = a.work + w.alpha + (int64_t)g * m;
     const double* cd = a.work + w.cdiag + (int64_t)g * m;
     const double* L = a.K + (int64_t)g * m * a.ld;
-    const double log2pi = 1.8378770664093454836;
-    double sum = 0.0;          // threads 0..3: y.alpha, sum log L_ii, loo_logp, sum (alpha / c)^2
-    for (int i0 = 0; i0 < m; i0 += 256) {
-        const int i = i0 + tid;
-        if (i < m) {
-            const double yi = a.y[i], al = alpha[i], c = cd[i];
-            const double r = al / c, mean = yi - r, var = 1.0 / c, d = yi - mean;
-            lm[i] = mean;
-            lv[i] = var;
-            term[0][tid] = yi * al;
-            term[1][tid] = log(L[(int64_t)i * a.ld + i]);
-            term[2][tid] = -0.5 * log(var) - d * d / (2.0 * var) - 0.5 * log2pi;
-            term[3][tid] = r * r;
-        }
-        __syncthreads();
-        if (tid < 4) {
-            const int cnt = min(256, m - i0);
-            for (int e = 0; e < cnt; e++) sum += term[tid][e];
-        }
-        __syncthreads();
-    }
+    // threads 0..3: y.alpha, sum log L_ii, loo_logp, sum (alpha / c)^2
+    const double sum = serial_sums(m, term, [&](int i) {
+        const double yi = a.y[i], al = alpha[i], c = cd[i];
+        const double r = al / c, mean = yi - r, var = 1.0 / c, d = yi - mean;
+        lm[i] = mean;
+        lv[i] = var;
+        term[0][tid] = yi * al;
+        term[1][tid] = log(L[(int64_t)i * a.ld + i]);
+        term[2][tid] = -0.5 * log(var) - d * d / (2.0 * var) - 0.5 * LOG2PI;
+        term[3][tid] = r * r;
+    });
     if (tid == 0) term[0][0] = sum;
     if (tid == 1) term[1][0] = sum;
     __syncthreads();
-    if (tid == 0) sc[0] = -0.5 * term[0][0] - term[1][0] - 0.5 * (double)m * log2pi;
+    if (tid == 0) sc[0] = lml_value(term[0][0], term[1][0], m);
     if (tid == 2) sc[1] = sum;
     if (tid == 3) sc[2] = sum / (double)m;
 }
@@ -284,45 +234,55 @@ extern "C" int64_t ital_gp_evidence_workspace(int m, int G) {
     return layout(m, G).total;
 }
 
-extern "C" int ital_gp_evidence(const ital_evidence_desc* d, hipStream_t stream) {
-    if (!d) return ital_fail(-22, "ital_gp_evidence: NULL descriptor");
-    if (!d->XT || !d->XTn || !d->y || !d->params || !d->K || !d->scores || !d->info || !d->loo_mean || !d->loo_var ||
-        !d->status || !d->work)
-        return ital_fail(-22, "ital_gp_evidence: NULL pointer");
-    if (d->m < 1 || d->G < 1) return ital_fail(-22, "ital_gp_evidence: m and G must be at least 1");
-    if (d->G > 65535) return ital_fail(-22, "ital_gp_evidence: more than 65535 candidates per call");
-    if (d->m > (1 << 22)) return ital_fail(-22, "ital_gp_evidence: matrix too large");
-    if (d->ldx <= 0 || d->ldx % 16 != 0) return ital_fail(-22, "ital_gp_evidence: ldx must be a positive multiple of 16");
-    if (d->ld < d->m) return ital_fail(-22, "ital_gp_evidence: ld must be at least m");
-    if (d->ldm < d->m) return ital_fail(-22, "ital_gp_evidence: ldm must be at least m");
-    const Layout w = layout(d->m, d->G);
-    if (d->work_doubles < w.total)
-        return ital_fail(-22, "ital_gp_evidence: work smaller than ital_gp_evidence_workspace(m, G)");
-    const int m = d->m, G = d->G;
-    auto mark = [&](int k) {
-        return (d->ev && hipEventRecord((hipEvent_t)d->ev[k], stream) != hipSuccess)
-                   ? ital_fail(-5, "ital_gp_evidence: hipEventRecord failed") : 0;
-    };
-    double* const* Kp = (double* const*)(d->work + w.Kp);
-    double* const* yp = (double* const*)(d->work + w.yp);
-    const int64_t* ldv = (const int64_t*)(d->work + w.ldv);
-    const int* nv = (const int*)(d->work + w.nv);
-    EvArgs a = {d->y, m, G, d->K, d->ld, d->scores, d->info, d->loo_mean, d->loo_var, d->ldm, d->work};
+// The checks and the prologue of both chains (evidence_chain.h).
+int ital::evidence::chain_check(const ChainArgs& c, const char* who) {
+    if (!c.XT || !c.XTn || !c.y || !c.params || !c.K || !c.info || !c.status || !c.work) return chain_fail(-22, who, "NULL pointer");
+    if (c.m < 1 || c.G < 1) return chain_fail(-22, who, "m and G must be at least 1");
+    if (c.G > 65535) return chain_fail(-22, who, "more than 65535 candidates per call");
+    if (c.m > (1 << 22)) return chain_fail(-22, who, "matrix too large");
+    if (c.ldx <= 0 || c.ldx % 16 != 0) return chain_fail(-22, who, "ldx must be a positive multiple of 16");
+    if (c.ld < c.m) return chain_fail(-22, who, "ld must be at least m");
+    return 0;
+}
+
+int ital::evidence::chain_prologue(const ChainArgs& c, const char* who, hipStream_t stream) {
     int rc;
-    ITAL_LAUNCH(evidence_setup_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
-    if ((rc = ital_check_launch("ital_gp_evidence(setup)"))) return rc;
-    if ((rc = mark(0))) return rc;
-    if ((rc = launch_gram_grid(d->XT, d->XTn, m, d->ldx, d->params, G, d->K, d->ld, stream))) return rc;
-    if ((rc = mark(1))) return rc;
-    if ((rc = ital_chol_batched(Kp, nv, ldv, G, m, d->info, d->status, stream))) return rc;
-    if ((rc = mark(2))) return rc;
-    if ((rc = ital_chol_solve_batched(Kp, nv, ldv, yp, G, d->info, stream))) return rc;
-    if ((rc = mark(3))) return rc;
-    InvdArgs v = {Kp, ldv, m, d->info, d->work + w.cdiag, m, d->work + w.M};
+    if ((rc = chain_check(c, who))) return rc;
+    const int m = c.m, G = c.G;
+    const Layout w = layout(m, G);
+    double* const* Kp = (double* const*)(c.work + w.Kp);
+    double* const* yp = (double* const*)(c.work + w.yp);
+    const int64_t* ldv = (const int64_t*)(c.work + w.ldv);
+    const int* nv = (const int*)(c.work + w.nv);
+    SetupArgs s = {c.y, m, G, c.K, c.ld, c.work};
+    ITAL_LAUNCH(chain_setup_kernel, dim3((unsigned)G), dim3(256), 0, stream, s);
+    if ((rc = chain_launched(who, "setup"))) return rc;
+    if ((rc = chain_mark(c.ev, 0, stream, who))) return rc;
+    if ((rc = launch_gram_grid(c.XT, c.XTn, m, c.ldx, c.params, G, c.K, c.ld, stream))) return rc;
+    if ((rc = chain_mark(c.ev, 1, stream, who))) return rc;
+    if ((rc = ital_chol_batched(Kp, nv, ldv, G, m, c.info, c.status, stream))) return rc;
+    if ((rc = chain_mark(c.ev, 2, stream, who))) return rc;
+    if ((rc = ital_chol_solve_batched(Kp, nv, ldv, yp, G, c.info, stream))) return rc;
+    if ((rc = chain_mark(c.ev, 3, stream, who))) return rc;
+    InvdArgs v = {Kp, ldv, m, c.info, c.work + w.cdiag, m, c.work + w.M};
     ITAL_LAUNCH(inv_diag_batched_kernel, dim3((unsigned)G), dim3(256), 0, stream, v);
-    if ((rc = ital_check_launch("ital_gp_evidence(inverse diagonals)"))) return rc;
-    if ((rc = mark(4))) return rc;
-    ITAL_LAUNCH(evidence_reduce_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
-    if ((rc = ital_check_launch("ital_gp_evidence(reduction)"))) return rc;
-    return mark(5);
+    if ((rc = chain_launched(who, "inverse diagonals"))) return rc;
+    return chain_mark(c.ev, 4, stream, who);
+}
+
+extern "C" int ital_gp_evidence(const ital_evidence_desc* d, hipStream_t stream) {
+    const char* who = "ital_gp_evidence";
+    if (!d) return chain_fail(-22, who, "NULL descriptor");
+    if (!d->scores || !d->loo_mean || !d->loo_var) return chain_fail(-22, who, "NULL pointer");
+    const ChainArgs c = {d->XT, d->XTn, d->ldx, d->y, d->m, d->params, d->G, d->K, d->ld, d->info, d->status, d->work, d->ev};
+    int rc;
+    if ((rc = chain_check(c, who))) return rc;
+    if (d->ldm < d->m) return chain_fail(-22, who, "ldm must be at least m");
+    if (d->work_doubles < layout(d->m, d->G).total)
+        return chain_fail(-22, who, "work smaller than ital_gp_evidence_workspace(m, G)");
+    if ((rc = chain_prologue(c, who, stream))) return rc;
+    EvArgs a = {d->y, d->m, d->G, d->K, d->ld, d->scores, d->info, d->loo_mean, d->loo_var, d->ldm, d->work};
+    ITAL_LAUNCH(evidence_reduce_kernel, dim3((unsigned)d->G), dim3(256), 0, stream, a);
+    if ((rc = chain_launched(who, "reduction"))) return rc;
+    return chain_mark(d->ev, 5, stream, who);
 }

@@ -4,27 +4,26 @@
 //
 //   ital_sqdist_lower               the squared distances every candidate shares, with the bits ital_gram_grid forms
 //   ital_chol_gram_inverse_batched  W = M^T M, the lower triangle of K^-1, from the inverse factors M = L^-1
-//   ital_gp_evidence_grad           setup, ital_gram_grid, ital_chol_batched, ital_chol_solve_batched,
-//                                   ital_chol_inv_diag_batched, squared distances, fused product, reduction
+//   ital_gp_evidence_grad           the prologue of ital_gp_evidence (setup, Gram grid, ital_chol_batched,
+//                                   ital_chol_solve_batched, inverse diagonals), squared distances, fused product, reduction
 //
-// The five leading stages are the entry points ital_gp_evidence runs, with the same arguments: factor, alpha and inverse
-// diagonal have its bits, and the reduction restates its two serial sums, so lml has them too.  The product is the 128 x 128
-// LDS-staged v_mfma_f64_16x16x4_f64 tile of mfma_tile.h (its LDS layout and mfma_stage) with BOTH operands read k-major
-// behind predicates (tile_tn below): M is stored [k][i], W_ij = sum_k M[k][i] M[k][j] runs down its columns, and a run of 16
-// neighbouring columns of one row k is one 128-byte read.  In the chain W never reaches memory: the epilogue turns a tile
-// into two numbers.
+// The five leading launches are chain_prologue (evidence_chain.h), the host function ital_gp_evidence runs, and the reduction
+// adds y.alpha and sum log L_ii through the same serial_sums and lml_value: factor, alpha, inverse diagonal and lml have its
+// bits because they come from the same code.  The product is the 128 x 128 LDS-staged v_mfma_f64_16x16x4_f64 tile of
+// mfma_tile.h (its LDS layout and mfma_stage) with BOTH operands read k-major behind predicates (tile_tn below): M is stored
+// [k][i], W_ij = sum_k M[k][i] M[k][j] runs down its columns, and a run of 16 neighbouring columns of one row k is one
+// 128-byte read.  In the chain W never reaches memory: the epilogue turns a tile into two numbers.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "evidence_chain.h"
 #include "ital_evidence_grad.h"
-#include "ital_internal.h"
-#include "mfma_tile.h"
 
 namespace ital {
 namespace evidence_grad {
 
-using namespace ital::tile;
+using namespace ital::evidence;
 
 // ------------------------------------------------------------------------------------------------- squared distances
 struct DistArgs {
@@ -32,41 +31,26 @@ struct DistArgs {
     double* D; int64_t ld;
 };
 
-// grid: lower tile pairs.  gram_grid_kernel up to its candidate loop: the same operands, tile and expression.
+// grid: lower tile pairs.  The tile gram_grid_kernel forms before its candidate loop (sqdist_tile), stored.
 __global__ __launch_bounds__(256, 2) void sqdist_lower_kernel(DistArgs a) {
     __shared__ StageLds lds;
     const int64_t m = a.m;
-    int ti, tj;
-    tri_pair(blockIdx.x, ti, tj);
-    const int64_t i0 = (int64_t)ti * T, j0 = (int64_t)tj * T;
-    if (i0 >= m) return;
-    int sk, srow;
-    stage_role(sk, srow);
-    const double* pa[4];
-    const double* pb[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {     // rows past m: the last row (computed, never stored)
-        pa[u] = a.XT + min(i0 + srow + 8 * u, m - 1) * a.ldx + sk;
-        pb[u] = a.XT + min(j0 + srow + 8 * u, m - 1) * a.ldx + sk;
-    }
     d4 acc[4][4];
-    zero_acc(acc);
-    tile_nt(pa, pb, a.ldx, lds, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t iw, jw;
+    if (!sqdist_tile(a.XT, a.xn, m, a.ldx, lds, acc, iw, jw)) return;
+    const int lane = threadIdx.x & 63;
     const int col = lane & 15, kg = lane >> 4;
-    const int64_t iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
+    // for_each_lower's walk, written out: through the helper the kernel takes 32 SGPRs instead of 30
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const int64_t j = jw + 16 * q + col;
-        const double bnj = a.xn[min(j, m - 1)];
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            if (iw + 16 * p >= m || jw + 16 * q > iw + 16 * p + 15) continue;     // nothing at or below the diagonal
+            if (iw + 16 * p >= m || jw + 16 * q > iw + 16 * p + 15) continue;
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
                 const int64_t i = iw + 16 * p + kg + 4 * reg;
-                const double ani = a.xn[min(i, m - 1)];
-                if (i < m && j <= i) a.D[i * a.ld + j] = rbf_sqdist(ani, bnj, acc[p][q][reg]);
+                if (i < m && j <= i) a.D[i * a.ld + j] = acc[p][q][reg];
             }
         }
     }
@@ -147,50 +131,28 @@ __global__ __launch_bounds__(256, 2) void gram_inverse_kernel(ProdArgs a) {
         };
         tile_tn(fa, fb, i0, n, lds, acc);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, kg = lane >> 4;
+    const int wave = threadIdx.x >> 6;
     const int iw = i0 + 64 * (wave >> 1), jw = j0 + 64 * (wave & 1);
     if (!FUSED) {
         double* W = a.W + (int64_t)g * n * a.ldw;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int j = jw + 16 * q + col;
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                if (iw + 16 * p >= n || jw + 16 * q > iw + 16 * p + 15) continue;
-#pragma unroll
-                for (int reg = 0; reg < 4; reg++) {
-                    const int i = iw + 16 * p + kg + 4 * reg;
-                    if (i < n && j <= i) W[(int64_t)i * a.ldw + j] = skip ? __builtin_nan("") : acc[p][q][reg];
-                }
-            }
-        }
+        for_each_lower(iw, jw, n, [&](int p, int q, int reg, int i, int j) {
+            W[(int64_t)i * a.ldw + j] = skip ? __builtin_nan("") : acc[p][q][reg];
+        });
         return;
     }
     const double l = a.params[3 * (int64_t)g], var = a.params[3 * (int64_t)g + 1];
     const double s = -2.0 * l * l;
     const double* alpha = a.alpha + (int64_t)g * n;
-    double sv = 0.0, sd = 0.0;
+    double sv = 0.0, sd = 0.0, aj[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int j = jw + 16 * q + col;
-        const double aj = alpha[min(j, n - 1)];
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            if (iw + 16 * p >= n || jw + 16 * q > iw + 16 * p + 15) continue;
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++) {
-                const int i = iw + 16 * p + kg + 4 * reg;
-                if (i < n && j <= i) {
-                    const double d = a.D[(int64_t)i * a.ldd + j];
-                    double t = (alpha[i] * aj - acc[p][q][reg]) * (var * exp(d / s));
-                    if (j < i) t += t;
-                    sv += t;
-                    sd += t * d;
-                }
-            }
-        }
-    }
+    for (int q = 0; q < 4; q++) aj[q] = alpha[min(jw + 16 * q + (int)(threadIdx.x & 15), n - 1)];
+    for_each_lower(iw, jw, n, [&](int p, int q, int reg, int i, int j) {
+        const double d = a.D[(int64_t)i * a.ldd + j];
+        double t = (alpha[i] * aj[q] - acc[p][q][reg]) * (var * exp(d / s));
+        if (j < i) t += t;
+        sv += t;
+        sd += t * d;
+    });
     double (*red)[256] = (double (*)[256]) & lds[0][0][0][0];     // tile_tn ended with a barrier: the stage buffers are free
     const int tid = threadIdx.x;
     red[0][tid] = sv;
@@ -207,23 +169,18 @@ __global__ __launch_bounds__(256, 2) void gram_inverse_kernel(ProdArgs a) {
 }
 
 // --------------------------------------------------------------------------------------------- setup and the reduction
-struct Layout {          // of the workspace of ital_gp_evidence_grad, in doubles from its start
-    int64_t alpha, cdiag, M, Kp, yp, ldv, nv, D, part, pairs, total;
+struct GradLayout {      // of the workspace of ital_gp_evidence_grad: that of ital_gp_evidence, then D and the partials
+    Layout ev;
+    int64_t D, part, pairs, total;
 };
 
-__host__ __device__ inline Layout layout(int64_t m, int64_t G) {
-    Layout w;
+__host__ __device__ inline GradLayout grad_layout(int64_t m, int64_t G) {
+    GradLayout w;
     const int64_t tn = (m + T - 1) / T;
     w.pairs = tn * (tn + 1) / 2;
-    w.alpha = 0;
-    w.cdiag = w.alpha + G * m;
-    w.M = w.cdiag + G * m;          // ital_chol_inv_diag_batched's workspace
-    w.Kp = w.M + G * m * m;
-    w.yp = w.Kp + G;
-    w.ldv = w.yp + G;
-    w.nv = w.ldv + G;               // n as int: half of it used
-    w.D = w.nv + G;                 // [m][m], shared by the candidates
-    w.part = w.D + m * m;
+    w.ev = layout(m, G);
+    w.D = w.ev.total;               // [m][m], shared by the candidates
+    w.part = w.D + m * m;           // [G][pairs][2]
     w.total = w.part + G * w.pairs * 2;
     return w;
 }
@@ -236,24 +193,9 @@ struct GradArgs {
     double* work;
 };
 
-// Workgroup g: the entries of the batched calls' argument arrays for candidate g, and y as the solve's right-hand side.
-__global__ __launch_bounds__(256) void grad_setup_kernel(GradArgs a) {
-    const int g = blockIdx.x;
-    const Layout w = layout(a.m, a.G);
-    double* alpha = a.work + w.alpha + (int64_t)g * a.m;
-    if (threadIdx.x == 0) {
-        ((double**)(a.work + w.Kp))[g] = a.K + (int64_t)g * a.m * a.ld;
-        ((double**)(a.work + w.yp))[g] = alpha;
-        ((int64_t*)(a.work + w.ldv))[g] = a.ld;
-        ((int*)(a.work + w.nv))[g] = a.m;
-    }
-    for (int i = threadIdx.x; i < a.m; i += 256) alpha[i] = a.y[i];
-}
-
-// Workgroup g: lml and the three gradient components of candidate g.  The terms of 256 samples at a time are formed by all
-// threads, then four threads add one kind each, i ascending -- y.alpha and sum log L_ii as evidence_reduce_kernel adds them
-// (the same terms, order and closing expression: the same bits), alpha.alpha and sum c_i likewise.  Thread 4 adds the tile
-// pairs' partials in ascending tile order.
+// Workgroup g: lml and the three gradient components of candidate g.  y.alpha, sum log L_ii, alpha.alpha and sum c_i are
+// serial_sums, the first two and lml_value as evidence_reduce_kernel calls them.  Thread 4 adds the tile pairs' partials in
+// ascending tile order.
 __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs a) {
     __shared__ double term[4][256];
     __shared__ double tot[6];
@@ -264,28 +206,18 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs a) {
         if (tid < 3) gr[tid] = __builtin_nan("");
         return;
     }
-    const Layout w = layout(m, a.G);
-    const double* alpha = a.work + w.alpha + (int64_t)g * m;
-    const double* cd = a.work + w.cdiag + (int64_t)g * m;
+    const GradLayout w = grad_layout(m, a.G);
+    const double* alpha = a.work + w.ev.alpha + (int64_t)g * m;
+    const double* cd = a.work + w.ev.cdiag + (int64_t)g * m;
     const double* L = a.K + (int64_t)g * m * a.ld;
-    const double log2pi = 1.8378770664093454836;
-    double sum = 0.0;          // threads 0..3: y.alpha, sum log L_ii, alpha.alpha, sum c_i
-    for (int i0 = 0; i0 < m; i0 += 256) {
-        const int i = i0 + tid;
-        if (i < m) {
-            const double yi = a.y[i], al = alpha[i];
-            term[0][tid] = yi * al;
-            term[1][tid] = log(L[(int64_t)i * a.ld + i]);
-            term[2][tid] = al * al;
-            term[3][tid] = cd[i];
-        }
-        __syncthreads();
-        if (tid < 4) {
-            const int cnt = min(256, m - i0);
-            for (int e = 0; e < cnt; e++) sum += term[tid][e];
-        }
-        __syncthreads();
-    }
+    // threads 0..3: y.alpha, sum log L_ii, alpha.alpha, sum c_i
+    const double sum = serial_sums(m, term, [&](int i) {
+        const double yi = a.y[i], al = alpha[i];
+        term[0][tid] = yi * al;
+        term[1][tid] = log(L[(int64_t)i * a.ld + i]);
+        term[2][tid] = al * al;
+        term[3][tid] = cd[i];
+    });
     if (tid == 4) {
         const double* part = a.work + w.part + (int64_t)g * w.pairs * 2;
         double sv = 0.0, sd = 0.0;
@@ -301,7 +233,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs a) {
     if (tid == 2) tot[2] = sum;
     if (tid == 3) tot[3] = sum;
     __syncthreads();
-    if (tid == 0) a.values[g] = -0.5 * term[0][0] - term[1][0] - 0.5 * (double)m * log2pi;
+    if (tid == 0) a.values[g] = lml_value(term[0][0], term[1][0], m);
     if (tid == 1) {
         const double l = a.params[3 * (int64_t)g], noise = a.params[3 * (int64_t)g + 2];
         gr[0] = 0.5 * tot[5] / (l * l);
@@ -347,52 +279,28 @@ extern "C" int ital_chol_gram_inverse_batched(const double* M, int n, int count,
 
 extern "C" int64_t ital_gp_evidence_grad_workspace(int m, int G) {
     if (m < 1 || G < 1) return 0;
-    return layout(m, G).total;
+    return grad_layout(m, G).total;
 }
 
 extern "C" int ital_gp_evidence_grad(const ital_evidence_grad_desc* d, hipStream_t stream) {
-    if (!d) return ital_fail(-22, "ital_gp_evidence_grad: NULL descriptor");
-    if (!d->XT || !d->XTn || !d->y || !d->params || !d->K || !d->values || !d->grad || !d->info || !d->status || !d->work)
-        return ital_fail(-22, "ital_gp_evidence_grad: NULL pointer");
-    if (d->m < 1 || d->G < 1) return ital_fail(-22, "ital_gp_evidence_grad: m and G must be at least 1");
-    if (d->G > 65535) return ital_fail(-22, "ital_gp_evidence_grad: more than 65535 candidates per call");
-    if (d->m > (1 << 22)) return ital_fail(-22, "ital_gp_evidence_grad: matrix too large");
-    if (d->ldx <= 0 || d->ldx % 16 != 0) return ital_fail(-22, "ital_gp_evidence_grad: ldx must be a positive multiple of 16");
-    if (d->ld < d->m) return ital_fail(-22, "ital_gp_evidence_grad: ld must be at least m");
-    const Layout w = layout(d->m, d->G);
-    if (d->work_doubles < w.total)
-        return ital_fail(-22, "ital_gp_evidence_grad: work smaller than ital_gp_evidence_grad_workspace(m, G)");
+    const char* who = "ital_gp_evidence_grad";
+    if (!d) return chain_fail(-22, who, "NULL descriptor");
+    if (!d->values || !d->grad) return chain_fail(-22, who, "NULL pointer");
     const int m = d->m, G = d->G;
-    auto mark = [&](int k) {
-        return (d->ev && hipEventRecord((hipEvent_t)d->ev[k], stream) != hipSuccess)
-                   ? ital_fail(-5, "ital_gp_evidence_grad: hipEventRecord failed") : 0;
-    };
-    double* const* Kp = (double* const*)(d->work + w.Kp);
-    double* const* yp = (double* const*)(d->work + w.yp);
-    const int64_t* ldv = (const int64_t*)(d->work + w.ldv);
-    const int* nv = (const int*)(d->work + w.nv);
-    GradArgs a = {d->y, m, G, d->params, d->K, d->ld, d->values, d->grad, d->info, d->work};
+    const ChainArgs c = {d->XT, d->XTn, d->ldx, d->y, m, d->params, G, d->K, d->ld, d->info, d->status, d->work, d->ev};
     int rc;
-    ITAL_LAUNCH(grad_setup_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
-    if ((rc = ital_check_launch("ital_gp_evidence_grad(setup)"))) return rc;
-    if ((rc = mark(0))) return rc;
-    if ((rc = ital_gram_grid(d->XT, d->XTn, m, d->ldx, d->params, G, d->K, d->ld, stream))) return rc;
-    if ((rc = mark(1))) return rc;
-    if ((rc = ital_chol_batched(Kp, nv, ldv, G, m, d->info, d->status, stream))) return rc;
-    if ((rc = mark(2))) return rc;
-    if ((rc = ital_chol_solve_batched(Kp, nv, ldv, yp, G, d->info, stream))) return rc;
-    if ((rc = mark(3))) return rc;
-    if ((rc = ital_chol_inv_diag_batched(Kp, ldv, m, G, d->info, d->work + w.cdiag, m, d->work + w.M, (int64_t)G * m * m,
-                                         stream)))
-        return rc;
-    if ((rc = mark(4))) return rc;
+    if ((rc = chain_check(c, who))) return rc;
+    const GradLayout w = grad_layout(m, G);
+    if (d->work_doubles < w.total) return chain_fail(-22, who, "work smaller than ital_gp_evidence_grad_workspace(m, G)");
+    if ((rc = chain_prologue(c, who, stream))) return rc;
     if ((rc = launch_sqdist(d->XT, d->XTn, m, d->ldx, d->work + w.D, m, stream))) return rc;
-    if ((rc = mark(5))) return rc;
-    ProdArgs p = {d->work + w.M, m, d->info, nullptr, 0, d->work + w.D, m, d->work + w.alpha, d->params, d->work + w.part};
+    if ((rc = chain_mark(d->ev, 5, stream, who))) return rc;
+    ProdArgs p = {d->work + w.ev.M, m, d->info, nullptr, 0, d->work + w.D, m, d->work + w.ev.alpha, d->params, d->work + w.part};
     ITAL_LAUNCH(gram_inverse_kernel<true>, dim3((unsigned)w.pairs, (unsigned)G), dim3(256), 0, stream, p);
-    if ((rc = ital_check_launch("ital_gp_evidence_grad(product)"))) return rc;
-    if ((rc = mark(6))) return rc;
+    if ((rc = chain_launched(who, "product"))) return rc;
+    if ((rc = chain_mark(d->ev, 6, stream, who))) return rc;
+    GradArgs a = {d->y, m, G, d->params, d->K, d->ld, d->values, d->grad, d->info, d->work};
     ITAL_LAUNCH(grad_reduce_kernel, dim3((unsigned)G), dim3(256), 0, stream, a);
-    if ((rc = ital_check_launch("ital_gp_evidence_grad(reduction)"))) return rc;
-    return mark(7);
+    if ((rc = chain_launched(who, "reduction"))) return rc;
+    return chain_mark(d->ev, 7, stream, who);
 }

@@ -35,6 +35,30 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _candidate_params(model, params_list):
+    """float64 [G, 3] (length_scale, var, noise) of hyper-parameter candidates: dicts with `length_scale`, `var`, `noise`;
+    what one leaves out is `model`'s current value.  TypeError for any other key, ValueError for a non-positive length_scale
+    or var.  evidence(), evidence_grad() and tune.session_scores read their candidates through this; an array it returned
+    passes through (session_scores parses once, then hands evidence() the array)."""
+    if isinstance(params_list, np.ndarray):
+        if params_list.dtype != np.float64 or params_list.ndim != 2 or params_list.shape[1] != 3:
+            raise TypeError("candidates as an array are float64 [G, 3]")
+        if not (params_list[:, :2] > 0).all():
+            raise ValueError("length_scale and var must be positive")
+        return np.ascontiguousarray(params_list)
+    rows = []
+    for p in params_list:
+        unknown = set(p) - {"length_scale", "var", "noise"}
+        if unknown:
+            raise TypeError("unexpected GP parameters: %s" % ", ".join(sorted(unknown)))
+        row = (float(p.get("length_scale", model.length_scale)), float(p.get("var", model.var)),
+               float(p.get("noise", model.noise)))
+        if not (row[0] > 0 and row[1] > 0):
+            raise ValueError("length_scale and var must be positive")
+        rows.append(row)
+    return np.array(rows, dtype=np.float64).reshape(len(rows), 3)
+
+
 def appends_after_remove(appends, p):
     """`appends` (sizes of the calls that built the labelled set, in order; negative: a group of queries) once the sample at
     labelled position `p` has left: the group that held it shrinks by one -- possibly to 0, which load_state_dict skips --
@@ -708,6 +732,46 @@ class GaussianProcess(object):
                 self._replicate_mean()
         return self
 
+    def _evidence_run(self, params_list, max_bytes, events, shapes, chunk_of, desc_cls, entry, workspace, n_events, outputs):
+        """What evidence() and evidence_grad() share: the candidates go through `entry` (descriptor `desc_cls`, workspace
+        function `workspace`) in chunks of at most `chunk_of(max_bytes)`, with y, the parameters, the Grams, the workspace,
+        info and a status word of the call's own on the device; `events` (`n_events` of them) reach the last chunk only.
+        `shapes`: name -> shape of one candidate's entry of each returned float64 array; `ok` [G] bool is added.
+        `outputs(d, chunk)` allocates the chunk's output buffers, names them in the descriptor and returns
+        download(out, g0, c), which copies the first c candidates' results to out[...][g0:g0 + c]."""
+        if self.m == 0:
+            raise RuntimeError("the GP has not been fitted")
+        prm = _candidate_params(self, params_list)
+        G, m, dev = len(prm), self.m, self.device
+        out = {k: np.empty((G,) + s) for k, s in shapes.items()}
+        out["ok"] = np.zeros(G, dtype=bool)
+        if G == 0:
+            return out
+        chunk = min(G, chunk_of(max_bytes))
+        with torch.cuda.device(dev):
+            yd = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(dev)
+            pd = torch.from_numpy(prm).to(dev)
+            K = torch.empty(chunk * m * m, dtype=torch.float64, device=dev)
+            need = int(workspace(m, chunk))
+            work = torch.empty(need, dtype=torch.float64, device=dev)
+            info = torch.empty(chunk, dtype=torch.int32, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)      # the call's own word: the model's is not touched
+            d = desc_cls()
+            d.XT, d.XTn, d.ldx, d.y, d.m = _ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(yd), m
+            d.K, d.ld, d.info, d.status, d.work, d.work_doubles = _ptr(K), m, _ptr(info), _ptr(status), _ptr(work), need
+            download = outputs(d, chunk)
+            for g0 in range(0, G, chunk):
+                c = min(chunk, G - g0)
+                d.params, d.G = pd.data_ptr() + 24 * g0, c
+                ev = None
+                if events is not None and g0 + c == G:
+                    ev = (ctypes.c_void_p * n_events)(*[e.cuda_event for e in events])
+                d.ev = ctypes.addressof(ev) if ev is not None else None
+                check(entry(ctypes.byref(d), _stream()))
+                download(out, g0, c)                  # synchronises: the chunk's buffers are free again
+                out["ok"][g0:g0 + c] = info[:c].cpu().numpy() == 0
+        return out
+
     def evidence_chunk(self, max_bytes=1 << 30):
         """Candidates evidence() sends to the device at once so that their Grams, workspace and outputs stay below
         `max_bytes` (at most 65535, the limit of one ital_gp_evidence call); MemoryError if one candidate alone exceeds it."""
@@ -722,7 +786,8 @@ class GaussianProcess(object):
         model: for each dict of `params_list` (`length_scale`, optional `var` / `noise`; default: the model's current value)
         the log marginal likelihood and the closed-form leave-one-out quantities of include/ital_evidence.h.  Returns a dict
         of numpy arrays: `lml`, `loo_logp`, `loo_mse` [G], `ok` [G] bool (the candidate's Gram was positive definite;
-        otherwise -inf, -inf, +inf and NaN rows), `loo_mean`, `loo_var` [G, m].
+        otherwise -inf, -inf, +inf and NaN rows), `loo_mean`, `loo_var` [G, m].  `params_list` may also be the candidates as
+        a float64 [G, 3] array of (length_scale, var, noise) rows.
 
         The candidates go to the device in chunks whose Grams and workspace stay below `max_bytes` (ital_gp_evidence: a
         number of launches that does not depend on the chunk); a candidate's values do not depend on the chunking.  Reads
@@ -730,52 +795,24 @@ class GaussianProcess(object):
         they are.  Every rank computes the same thing locally: no collective.  RuntimeError for an unfitted model,
         ValueError for a non-positive length_scale / var, MemoryError if one candidate alone exceeds max_bytes.
         `events`: None, or six recorded torch events that bracket the five stages of the LAST chunk (tools/evidence_bench.py)."""
-        if self.m == 0:
-            raise RuntimeError("the GP has not been fitted")
-        prm = np.empty((len(params_list), 3), dtype=np.float64)
-        for g, p in enumerate(params_list):
-            unknown = set(p) - {"length_scale", "var", "noise"}
-            if unknown:
-                raise TypeError("unexpected GP parameters: %s" % ", ".join(sorted(unknown)))
-            prm[g] = (float(p.get("length_scale", self.length_scale)), float(p.get("var", self.var)),
-                      float(p.get("noise", self.noise)))
-            if not (prm[g, 0] > 0 and prm[g, 1] > 0):
-                raise ValueError("length_scale and var must be positive")
-        G, m, lib, dev = len(prm), self.m, self._lib, self.device
-        out = dict(lml=np.empty(G), loo_logp=np.empty(G), loo_mse=np.empty(G), ok=np.zeros(G, dtype=bool),
-                   loo_mean=np.empty((G, m)), loo_var=np.empty((G, m)))
-        if G == 0:
-            return out
-        chunk = min(G, self.evidence_chunk(max_bytes))
-        with torch.cuda.device(dev):
-            yd = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(dev)
-            pd = torch.from_numpy(prm).to(dev)
-            K = torch.empty(chunk * m * m, dtype=torch.float64, device=dev)
-            need = int(lib.ital_gp_evidence_workspace(m, chunk))
-            work = torch.empty(need, dtype=torch.float64, device=dev)
-            scores = torch.empty((chunk, 3), dtype=torch.float64, device=dev)
-            info = torch.empty(chunk, dtype=torch.int32, device=dev)
-            lm = torch.empty((chunk, m), dtype=torch.float64, device=dev)
-            lv = torch.empty((chunk, m), dtype=torch.float64, device=dev)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)      # the call's own word: the model's is not touched
-            d = _lib.ItalEvidenceDesc()
-            d.XT, d.XTn, d.ldx, d.y, d.m = _ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(yd), m
-            d.K, d.ld, d.scores, d.info, d.loo_mean, d.loo_var, d.ldm = _ptr(K), m, _ptr(scores), _ptr(info), _ptr(lm), _ptr(lv), m
-            d.status, d.work, d.work_doubles = _ptr(status), _ptr(work), need
-            for g0 in range(0, G, chunk):
-                c = min(chunk, G - g0)
-                d.params, d.G = pd.data_ptr() + 24 * g0, c
-                ev = None
-                if events is not None and g0 + c == G:
-                    ev = (ctypes.c_void_p * 6)(*[e.cuda_event for e in events])
-                d.ev = ctypes.addressof(ev) if ev is not None else None
-                check(lib.ital_gp_evidence(ctypes.byref(d), _stream()))
-                sc = scores[:c].cpu().numpy()         # synchronises: the chunk's buffers are free again
+        m = self.m
+
+        def outputs(d, chunk):
+            scores = torch.empty((chunk, 3), dtype=torch.float64, device=self.device)
+            lm = torch.empty((chunk, m), dtype=torch.float64, device=self.device)
+            lv = torch.empty((chunk, m), dtype=torch.float64, device=self.device)
+            d.scores, d.loo_mean, d.loo_var, d.ldm = _ptr(scores), _ptr(lm), _ptr(lv), m
+
+            def download(out, g0, c):
+                sc = scores[:c].cpu().numpy()
                 out["lml"][g0:g0 + c], out["loo_logp"][g0:g0 + c], out["loo_mse"][g0:g0 + c] = sc[:, 0], sc[:, 1], sc[:, 2]
-                out["ok"][g0:g0 + c] = info[:c].cpu().numpy() == 0
                 out["loo_mean"][g0:g0 + c] = lm[:c].cpu().numpy()
                 out["loo_var"][g0:g0 + c] = lv[:c].cpu().numpy()
-        return out
+            return download
+
+        return self._evidence_run(params_list, max_bytes, events, dict(lml=(), loo_logp=(), loo_mse=(), loo_mean=(m,), loo_var=(m,)),
+                                  self.evidence_chunk, _lib.ItalEvidenceDesc, self._lib.ital_gp_evidence,
+                                  self._lib.ital_gp_evidence_workspace, 6, outputs)
 
     def evidence_grad_chunk(self, max_bytes=1 << 30):
         """Candidates evidence_grad() sends to the device at once so that their Grams, workspace and outputs stay below
@@ -804,48 +841,19 @@ class GaussianProcess(object):
         MemoryError if one candidate alone exceeds max_bytes.
         `events`: None, or eight recorded torch events that bracket the seven stages of the LAST chunk
         (tools/evidence_grad_bench.py)."""
-        if self.m == 0:
-            raise RuntimeError("the GP has not been fitted")
-        prm = np.empty((len(params_list), 3), dtype=np.float64)
-        for g, p in enumerate(params_list):
-            unknown = set(p) - {"length_scale", "var", "noise"}
-            if unknown:
-                raise TypeError("unexpected GP parameters: %s" % ", ".join(sorted(unknown)))
-            prm[g] = (float(p.get("length_scale", self.length_scale)), float(p.get("var", self.var)),
-                      float(p.get("noise", self.noise)))
-            if not (prm[g, 0] > 0 and prm[g, 1] > 0):
-                raise ValueError("length_scale and var must be positive")
-        G, m, lib, dev = len(prm), self.m, self._lib, self.device
-        out = dict(lml=np.empty(G), grad=np.empty((G, 3)), ok=np.zeros(G, dtype=bool))
-        if G == 0:
-            return out
-        chunk = min(G, self.evidence_grad_chunk(max_bytes))
-        with torch.cuda.device(dev):
-            yd = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(dev)
-            pd = torch.from_numpy(prm).to(dev)
-            K = torch.empty(chunk * m * m, dtype=torch.float64, device=dev)
-            need = int(lib.ital_gp_evidence_grad_workspace(m, chunk))
-            work = torch.empty(need, dtype=torch.float64, device=dev)
-            values = torch.empty(chunk, dtype=torch.float64, device=dev)
-            grad = torch.empty((chunk, 3), dtype=torch.float64, device=dev)
-            info = torch.empty(chunk, dtype=torch.int32, device=dev)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)      # the call's own word: the model's is not touched
-            d = _lib.ItalEvidenceGradDesc()
-            d.XT, d.XTn, d.ldx, d.y, d.m = _ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(yd), m
-            d.K, d.ld, d.values, d.grad, d.info = _ptr(K), m, _ptr(values), _ptr(grad), _ptr(info)
-            d.status, d.work, d.work_doubles = _ptr(status), _ptr(work), need
-            for g0 in range(0, G, chunk):
-                c = min(chunk, G - g0)
-                d.params, d.G = pd.data_ptr() + 24 * g0, c
-                ev = None
-                if events is not None and g0 + c == G:
-                    ev = (ctypes.c_void_p * 8)(*[e.cuda_event for e in events])
-                d.ev = ctypes.addressof(ev) if ev is not None else None
-                check(lib.ital_gp_evidence_grad(ctypes.byref(d), _stream()))
-                out["lml"][g0:g0 + c] = values[:c].cpu().numpy()      # synchronises: the chunk's buffers are free again
+        def outputs(d, chunk):
+            values = torch.empty(chunk, dtype=torch.float64, device=self.device)
+            grad = torch.empty((chunk, 3), dtype=torch.float64, device=self.device)
+            d.values, d.grad = _ptr(values), _ptr(grad)
+
+            def download(out, g0, c):
+                out["lml"][g0:g0 + c] = values[:c].cpu().numpy()
                 out["grad"][g0:g0 + c] = grad[:c].cpu().numpy()
-                out["ok"][g0:g0 + c] = info[:c].cpu().numpy() == 0
-        return out
+            return download
+
+        return self._evidence_run(params_list, max_bytes, events, dict(lml=(), grad=(3,)), self.evidence_grad_chunk,
+                                  _lib.ItalEvidenceGradDesc, self._lib.ital_gp_evidence_grad,
+                                  self._lib.ital_gp_evidence_grad_workspace, 8, outputs)
 
     def check_status(self, status=None):
         """Raises if a kernel flagged a numerical failure.  `status`: the word as already downloaded (e.g. the OR over all

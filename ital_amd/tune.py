@@ -364,20 +364,18 @@ def session_scores(gp_or_learner, params_list, criterion='lml'):
     A candidate whose Gram is not positive definite scores -inf, with the warning of cross_validate_gp."""
     if criterion not in SESSION_CRITERIA:
         raise ValueError('criterion must be one of %s' % ', '.join(SESSION_CRITERIA))
-    params_list = [dict(p) for p in params_list]
-    for prm in params_list:
-        unknown = set(prm) - {'length_scale', 'var', 'noise'}
-        if unknown:
-            raise TypeError('unexpected GP parameters: %s' % ', '.join(sorted(unknown)))
+    from .gp import _candidate_params
     gp = _session_gp(gp_or_learner)
+    # refuses an unknown key or a non-positive value before any device work
+    prm = _candidate_params(gp, [dict(p) for p in params_list])
     if criterion == 'loo_ap':
         from sklearn.metrics import average_precision_score
         y = np.asarray(gp.y if gp.y is not None else [], dtype=np.float64)
         if not (np.any(y > 0) and np.any(y <= 0)):
             raise ValueError("criterion 'loo_ap' needs labels of both signs")
-    ev = gp.evidence(params_list)
+    ev = gp.evidence(prm)
     result = []
-    for g in range(len(params_list)):
+    for g in range(len(prm)):
         if not ev['ok'][g]:
             warnings.warn('Matrix is not positive semi-definite.', stacklevel=2)
             result.append(-np.inf)

@@ -128,6 +128,19 @@ def test_entry_points_refuse_bad_arguments_without_a_device():
         refused(lib.ital_chol_gram_inverse_batched(*[a[k] for k in order], None), "ital_chol_gram_inverse_batched")
 
 
+@pytest.mark.parametrize("G", [1, 3])
+@pytest.mark.parametrize("m", [1, 127, 128, 129, 257])
+def test_the_gradients_workspace_is_the_evidences_plus_distances_and_partials(m, G):
+    """ital_gp_evidence's workspace: alpha and the inverse diagonals [G][m] each, M [G][m][m], four tables of G entries.
+    ital_gp_evidence_grad's: that, then D [m][m] and two partials per candidate and lower pair of 128 x 128 tiles."""
+    from ital_amd import _lib
+    lib = _lib.load()
+    tn = (m + 127) // 128
+    pairs = tn * (tn + 1) // 2
+    assert lib.ital_gp_evidence_workspace(m, G) == 2 * G * m + G * m * m + 4 * G
+    assert lib.ital_gp_evidence_grad_workspace(m, G) - lib.ital_gp_evidence_workspace(m, G) == m * m + 2 * G * pairs
+
+
 def test_every_learner_has_fit_params():
     import ital_amd
     from ital_amd import baselines

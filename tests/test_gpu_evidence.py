@@ -8,7 +8,6 @@ every score, loo_mean, loo_var and inverse diagonal within 100 * cond(K) * 2^-52
 a backward-stable solve, the factor 100 for the growth with m and d; cond from numpy.linalg.cond, kept below 1e5, so the bar
 is at most 2e-9, the project's GP bar.  Every comparison prints its figure before it asserts (run with -s to see them).
 Run: python -m pytest tests -m gpu."""
-import ctypes
 import functools
 import os
 import sys
@@ -25,10 +24,11 @@ torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+from _evidence_inputs import CANDS, GUARD, _case, _evidence, _labels, _lib, _params, _stream, _upload  # noqa: E402
+
 EPS = 2.0 ** -52
 K_RTOL = 1e-12
 APPEND_ATOL = 2e-9       # set_params' bar (tests/test_gpu_rewhiten.py)
-GUARD = -7.0             # what output buffers hold before a call: nothing outside the documented part may change
 
 
 @pytest.fixture(scope="module")
@@ -67,71 +67,8 @@ def _within(got, want, cond, what):
     assert err <= bound, (what, err, bound, cond)
 
 
-def _labels(rng, m):
-    return np.where(rng.random(m) < 0.4, 1.0, -1.0)
-
-
 # ------------------------------------------------------------------------------------------------ the C ABI, directly
-def _lib():
-    from ital_amd import _lib
-    return _lib, _lib.lib()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _upload(X, dev):
-    """Feature rows zero padded to a multiple of 16 columns, and their squared norms (ital_row_norms)."""
-    L, lib = _lib()
-    m, d = X.shape
-    ldx = (d + 15) // 16 * 16
-    XT = torch.zeros((m, ldx), dtype=torch.float64, device=dev)
-    XT[:, :d] = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
-    XTn = torch.empty(m, dtype=torch.float64, device=dev)
-    L.check(lib.ital_row_norms(XT.data_ptr(), m, ldx, XTn.data_ptr(), _stream()))
-    return XT, XTn, ldx
-
-
-def _params(cands, dev):
-    return torch.tensor([[float(v) for v in c] for c in cands], dtype=torch.float64, device=dev)
-
-
-def _evidence(X, y, cands, dev, pad=0):
-    """ital_gp_evidence on G candidates; leading dimensions m + pad.  Returns host copies and the device tensors."""
-    L, lib = _lib()
-    XT, XTn, ldx = _upload(X, dev)
-    m, G = len(X), len(cands)
-    ld = ldm = m + pad
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
-    prm = _params(cands, dev)
-    K = torch.full((G, m, ld), GUARD, dtype=torch.float64, device=dev)
-    need = int(lib.ital_gp_evidence_workspace(m, G))
-    work = torch.empty(need, dtype=torch.float64, device=dev)
-    scores = torch.full((G, 3), GUARD, dtype=torch.float64, device=dev)
-    info = torch.full((G,), -1, dtype=torch.int32, device=dev)
-    lm = torch.full((G, ldm), GUARD, dtype=torch.float64, device=dev)
-    lv = torch.full((G, ldm), GUARD, dtype=torch.float64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    d = L.ItalEvidenceDesc()
-    d.XT, d.XTn, d.ldx, d.y, d.m, d.params, d.G = XT.data_ptr(), XTn.data_ptr(), ldx, yd.data_ptr(), m, prm.data_ptr(), G
-    d.K, d.ld, d.scores, d.info, d.loo_mean, d.loo_var, d.ldm = K.data_ptr(), ld, scores.data_ptr(), info.data_ptr(), \
-        lm.data_ptr(), lv.data_ptr(), ldm
-    d.status, d.work, d.work_doubles, d.ev = status.data_ptr(), work.data_ptr(), need, None
-    L.check(lib.ital_gp_evidence(ctypes.byref(d), _stream()))
-    torch.cuda.synchronize()
-    return dict(scores=scores, info=info, loo_mean=lm, loo_var=lv, status=int(status.item()), K=K, m=m)
-
-
-CANDS = {3: [(0.5, 1.0, 0.1), (0.8, 1.5, 0.3), (0.35, 0.7, 0.05)],
-         40: [(1.2, 1.0, 1e-4), (1.8, 1.5, 1e-3), (0.9, 0.7, 1e-6)]}
 SHAPES = [(m, d, G) for m in (1, 2, 17, 63, 64, 65, 129, 200) for d in (3, 40) for G in (1, 3)]
-
-
-def _case(m, d, G):
-    rng = np.random.default_rng(1000 * d + m)
-    X = rng.random((m, d))
-    return X, _labels(rng, m), CANDS[d][:G]
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,9 +2,9 @@
 csrc/evidence_grad.hip) and what is built on it: GaussianProcess.evidence_grad, tune.fit_session_params and
 ActiveRetrievalBase.fit_params.
 
-Inputs are those of tests/test_gpu_evidence.py, restated.  The references are computed here with numpy / scipy in float64
-(tests/_evidence_grad_ref.py), D from the same expansion |x_i|^2 + |x_j|^2 - 2 x_i.x_j.  No bound comes from a measurement
-on the device:
+Inputs are those of tests/test_gpu_evidence.py (tests/_evidence_inputs.py holds them for both).  The references are computed
+here with numpy / scipy in float64 (tests/_evidence_grad_ref.py), D from the same expansion |x_i|^2 + |x_j|^2 - 2 x_i.x_j.
+No bound comes from a measurement on the device:
 
 - D within rtol 1e-12 of the host's where |D| > 1e-9, else atol 1e-12 (the project's bar for RBF values);
 - W = K^-1 within 100 * cond(K) * 2^-52 of max(1, |inv|) of numpy.linalg.inv, cond < 1e5 (the bar of test_gpu_evidence.py);
@@ -31,9 +31,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import _evidence_grad_ref as ref  # noqa: E402
+from _evidence_inputs import CANDS, GUARD, _case, _evidence, _labels, _lib, _params, _stream, _upload  # noqa: E402
 
 EPS = 2.0 ** -52
-GUARD = -7.0             # what output buffers hold before a call: nothing outside the documented part may change
 WORST = {"grad": 0.0, "W": 0.0, "fd": 0.0}
 
 
@@ -44,59 +44,9 @@ def dev():
     return "cuda:0"
 
 
-def _labels(rng, m):
-    return np.where(rng.random(m) < 0.4, 1.0, -1.0)
-
-
-def _lib():
-    from ital_amd import _lib
-    return _lib, _lib.lib()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _upload(X, dev):
-    """Feature rows zero padded to a multiple of 16 columns, and their squared norms (ital_row_norms)."""
-    L, lib = _lib()
-    m, d = X.shape
-    ldx = (d + 15) // 16 * 16
-    XT = torch.zeros((m, ldx), dtype=torch.float64, device=dev)
-    XT[:, :d] = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
-    XTn = torch.empty(m, dtype=torch.float64, device=dev)
-    L.check(lib.ital_row_norms(XT.data_ptr(), m, ldx, XTn.data_ptr(), _stream()))
-    return XT, XTn, ldx
-
-
-def _params(cands, dev):
-    return torch.tensor([[float(v) for v in c] for c in cands], dtype=torch.float64, device=dev)
-
-
 def _evidence_lml(X, y, cands, dev, pad=0):
-    """ital_gp_evidence, the parent's entry point, on G candidates: the device tensor of its lml."""
-    L, lib = _lib()
-    XT, XTn, ldx = _upload(X, dev)
-    m, G = len(X), len(cands)
-    ld = ldm = m + pad
-    yd = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64)).to(dev)
-    prm = _params(cands, dev)
-    K = torch.empty((G, m, ld), dtype=torch.float64, device=dev)
-    need = int(lib.ital_gp_evidence_workspace(m, G))
-    work = torch.empty(need, dtype=torch.float64, device=dev)
-    scores = torch.full((G, 3), GUARD, dtype=torch.float64, device=dev)
-    info = torch.full((G,), -1, dtype=torch.int32, device=dev)
-    lm = torch.empty((G, ldm), dtype=torch.float64, device=dev)
-    lv = torch.empty((G, ldm), dtype=torch.float64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    d = L.ItalEvidenceDesc()
-    d.XT, d.XTn, d.ldx, d.y, d.m, d.params, d.G = XT.data_ptr(), XTn.data_ptr(), ldx, yd.data_ptr(), m, prm.data_ptr(), G
-    d.K, d.ld, d.scores, d.info, d.loo_mean, d.loo_var, d.ldm = K.data_ptr(), ld, scores.data_ptr(), info.data_ptr(), \
-        lm.data_ptr(), lv.data_ptr(), ldm
-    d.status, d.work, d.work_doubles, d.ev = status.data_ptr(), work.data_ptr(), need, None
-    L.check(lib.ital_gp_evidence(ctypes.byref(d), _stream()))
-    torch.cuda.synchronize()
-    return scores[:, 0].clone()
+    """ital_gp_evidence, the entry point this one extends, on G candidates: the device tensor of its lml."""
+    return _evidence(X, y, cands, dev, pad=pad)["scores"][:, 0].clone()
 
 
 def _grad(X, y, cands, dev, pad=0):
@@ -118,25 +68,19 @@ def _grad(X, y, cands, dev, pad=0):
     d.XT, d.XTn, d.ldx, d.y, d.m, d.params, d.G = XT.data_ptr(), XTn.data_ptr(), ldx, yd.data_ptr(), m, prm.data_ptr(), G
     d.K, d.ld, d.values, d.grad, d.info = K.data_ptr(), ld, values.data_ptr(), grad.data_ptr(), info.data_ptr()
     d.status, d.work, d.work_doubles, d.ev = status.data_ptr(), work.data_ptr(), need, None
+    before = int(lib.ital_launch_count())
     L.check(lib.ital_gp_evidence_grad(ctypes.byref(d), _stream()))
+    launches = int(lib.ital_launch_count()) - before
     torch.cuda.synchronize()
     assert float(values[G]) == GUARD and bool((grad[G] == GUARD).all()) and int(info[G]) == -1 and int(status[1]) == 0
     assert float(work[need]) == GUARD
     assert bool((K[:, :, m:] == GUARD).all())                           # nothing beyond column m of the Grams
     up = torch.triu(torch.ones((m, m), dtype=torch.bool, device=dev), 1)
     assert bool((K[:, :, :m][:, up] == GUARD).all())                    # nothing above their diagonals
-    return dict(values=values[:G], grad=grad[:G], info=info[:G], status=int(status[0].item()))
+    return dict(values=values[:G], grad=grad[:G], info=info[:G], status=int(status[0].item()), K=K, work=work, launches=launches)
 
 
-CANDS = {3: [(0.5, 1.0, 0.1), (0.8, 1.5, 0.3), (0.35, 0.7, 0.05)],
-         40: [(1.2, 1.0, 1e-4), (1.8, 1.5, 1e-3), (0.9, 0.7, 1e-6)]}
 SHAPES = [(m, d, G) for m in (1, 2, 17, 63, 64, 65, 127, 128, 129, 200, 257) for d in (3, 40) for G in (1, 3)]
-
-
-def _case(m, d, G):
-    rng = np.random.default_rng(1000 * d + m)
-    X = rng.random((m, d))
-    return X, _labels(rng, m), CANDS[d][:G]
 
 
 @functools.lru_cache(maxsize=None)
@@ -276,6 +220,34 @@ def test_a_candidate_gets_the_same_bits_alone_and_anywhere_in_a_batch(dev):
     for g in range(5):
         assert _same(middle, g, first, (g - 2) % 5) and _same(middle, g, last, (g - 3) % 5)
     assert bool(torch.isfinite(middle["grad"]).all())
+
+
+# ------------------------------------------------------------------------------------------------ the shared prologue
+@pytest.mark.parametrize("m,d,G", [(1, 3, 1), (64, 3, 3), (65, 40, 3), (129, 3, 3)])
+def test_both_chains_leave_the_same_prologue_state(dev, m, d, G):
+    """ital_gp_evidence and ital_gp_evidence_grad on the same inputs, K and the workspaces filled with the guard value, both
+    with leading dimension m: the same factors in K (and the same untouched rest of it), the same info, and the same alpha,
+    inverse diagonals and M at the head of the workspace.  The pointer tables behind M hold addresses and are not compared."""
+    X, y, cands = _case(m, d, G)
+    e, g = _evidence(X, y, cands, dev), _grad(X, y, cands, dev)
+    assert e["status"] == 0 and g["status"] == 0
+    assert torch.equal(e["K"], g["K"])
+    assert torch.equal(e["info"], g["info"])
+    head = 2 * G * m + G * m * m
+    assert torch.equal(e["work"][:head], g["work"][:head])
+    assert not bool((e["work"][:2 * G * m] == GUARD).any())             # alpha and the inverse diagonals were written
+    assert float(e["work"][e["need"]]) == GUARD                         # nothing behind ital_gp_evidence's workspace
+
+
+@pytest.mark.parametrize("m", [1, 65, 129])
+def test_the_gradient_costs_two_launches_more_and_neither_count_depends_on_G(dev, m):
+    counts = {}
+    for G in (1, 3):
+        X, y, cands = _case(m, 3, G)
+        counts[G] = (_evidence(X, y, cands, dev)["launches"], _grad(X, y, cands, dev)["launches"])
+        print("GRAD launches m %d G %d: evidence %d  evidence_grad %d" % ((m, G) + counts[G]))
+        assert counts[G][1] - counts[G][0] == 2
+    assert counts[1] == counts[3]
 
 
 def _gp(dev, X, ind, y, ls, **kw):
