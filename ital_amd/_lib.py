@@ -1,6 +1,6 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
-include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_ingest.h,
-include/ital_rows.h and include/ital_compact.h).
+include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_evidence_grad.h,
+include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h and include/ital_compact.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -267,6 +267,21 @@ EVIDENCE_GRAD_SIGNATURES = {
 }
 
 
+class ItalLooGradDesc(ctypes.Structure):
+    """ital_loo_grad_desc (include/ital_loo_grad.h): the labelled set, a chunk of candidates and where their leave-one-out
+    scores and gradients go."""
+    _fields_ = [("XT", c_void_p), ("XTn", c_void_p), ("ldx", c_int), ("y", c_void_p), ("m", c_int), ("params", c_void_p),
+                ("G", c_int), ("K", c_void_p), ("ld", c_int64), ("values", c_void_p), ("grad", c_void_p), ("info", c_void_p),
+                ("status", c_void_p), ("work", c_void_p), ("work_doubles", c_int64), ("ev", c_void_p)]
+
+
+#: the leave-one-out scores with their gradients in the log-parameters, declared in include/ital_loo_grad.h
+LOO_GRAD_SIGNATURES = {
+    "ital_gp_loo_grad": (c_int, [ctypes.POINTER(ItalLooGradDesc), c_void_p]),
+    "ital_gp_loo_grad_workspace": (c_int64, [c_int, c_int]),
+}
+
+
 #: element types of ital_ingest_rows (include/ital_ingest.h)
 INGEST_F64, INGEST_F32, INGEST_F16, INGEST_BF16 = 0, 1, 2, 3
 
@@ -323,7 +338,7 @@ def load(path=LIB_PATH):
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-            list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()):
+            list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

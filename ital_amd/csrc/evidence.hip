@@ -169,21 +169,21 @@ __global__ __launch_bounds__(256) void evidence_reduce_kernel(EvArgs a) {
     const double* L = a.K + (int64_t)g * m * a.ld;
     // threads 0..3: y.alpha, sum log L_ii, loo_logp, sum (alpha / c)^2
     const double sum = serial_sums(m, term, [&](int i) {
-        const double yi = a.y[i], al = alpha[i], c = cd[i];
-        const double r = al / c, mean = yi - r, var = 1.0 / c, d = yi - mean;
-        lm[i] = mean;
-        lv[i] = var;
+        const double yi = a.y[i], al = alpha[i];
+        const LooSample t = loo_sample(yi, al, cd[i]);
+        lm[i] = t.mean;
+        lv[i] = t.var;
         term[0][tid] = yi * al;
         term[1][tid] = log(L[(int64_t)i * a.ld + i]);
-        term[2][tid] = -0.5 * log(var) - d * d / (2.0 * var) - 0.5 * LOG2PI;
-        term[3][tid] = r * r;
+        term[2][tid] = t.logp;
+        term[3][tid] = t.sq;
     });
     if (tid == 0) term[0][0] = sum;
     if (tid == 1) term[1][0] = sum;
     __syncthreads();
     if (tid == 0) sc[0] = lml_value(term[0][0], term[1][0], m);
     if (tid == 2) sc[1] = sum;
-    if (tid == 3) sc[2] = sum / (double)m;
+    if (tid == 3) sc[2] = loo_mse_value(sum, m);
 }
 
 }  // namespace evidence

@@ -1,7 +1,8 @@
-// What ital_gp_evidence (evidence.hip) and ital_gp_evidence_grad (evidence_grad.hip) share, in one place: the workspace
-// layout, the prologue of five launches, the squared-distance tile, the walk over a wave's lower-triangle elements and the
-// serial sums that close both chains.  evidence_grad's factor, alpha, inverse diagonal, M and lml have evidence's bits
-// because both run this code, not because two files are kept in step.
+// What ital_gp_evidence (evidence.hip), ital_gp_evidence_grad (evidence_grad.hip) and ital_gp_loo_grad (loo_grad.hip) share,
+// in one place: the workspace layout, the prologue of five launches, the squared-distance tile, the walk over a wave's
+// lower-triangle elements, the k-major product tile, the serial sums that close the chains and the per-sample terms of lml and
+// the leave-one-out scores.  evidence_grad's factor, alpha, inverse diagonal, M and lml, and loo_grad's loo_logp and loo_mse,
+// have evidence's bits because all run this code, not because files are kept in step.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,7 +35,7 @@ __host__ __device__ inline Layout layout(int64_t m, int64_t G) {
 }
 
 // -------------------------------------------------------------------------------------------------------- prologue
-struct ChainArgs {       // the fields ital_evidence_desc and ital_evidence_grad_desc share
+struct ChainArgs {       // the fields ital_evidence_desc, ital_evidence_grad_desc and ital_loo_grad_desc share
     const double* XT; const double* XTn; int ldx; const double* y; int m; const double* params; int G;
     double* K; int64_t ld; int* info; int* status; double* work; void* const* ev;
 };
@@ -130,6 +131,44 @@ __device__ inline void for_each_lower(I iw, I jw, I n, F f) {
     }
 }
 
+// ------------------------------------------------------------------------------------- k-major product tile
+// acc[p][q] += sum over kbeg <= k < kend of A(k, r) B(k, c) for the 128 x 128 tile of a workgroup of 256 threads: wave
+// (wy, wx) owns tile rows 64 wy + 16 p + (kg + 4 reg) and tile columns 64 wx + 16 q + col (D layout of the f64 MFMA).
+// fa(k, r) / fb(k, c): the element of A at tile row r / of B at tile column c, both k-major; they return 0 outside their
+// operand (k at or past kend included).  Thread (k = tid / 16, tid % 16) stages eight runs of 16 columns of its k for each
+// operand, into the layout mfma_stage reads.  Register + LDS double buffer, one barrier per stage; ends with a barrier.
+template <class FA, class FB>
+__device__ inline void tile_tn(FA fa, FB fb, int kbeg, int kend, StageLds& lds, d4 acc[4][4]) {
+    const int kb = threadIdx.x >> 4, c16 = threadIdx.x & 15;
+    double ra[8], rb[8];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            ra[u] = fa(k0 + kb, c16 + 16 * u);
+            rb[u] = fb(k0 + kb, c16 + 16 * u);
+        }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            lds[buf][0][kb][c16 + 16 * u] = ra[u];
+            lds[buf][1][kb][c16 + 16 * u] = rb[u];
+        }
+    };
+    const int nstep = (kend - kbeg + KS - 1) / KS;
+    if (nstep <= 0) return;
+    fetch(kbeg);
+    stage(0);
+    __syncthreads();
+    for (int s_ = 0; s_ < nstep; s_++) {
+        const int buf = s_ & 1;
+        if (s_ + 1 < nstep) fetch(kbeg + (s_ + 1) * KS);
+        mfma_stage(lds, buf, acc);
+        if (s_ + 1 < nstep) stage(buf ^ 1);
+        __syncthreads();
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------- serial sums
 constexpr double LOG2PI = 1.8378770664093454836;
 
@@ -153,6 +192,20 @@ __device__ inline double serial_sums(int m, double (*term)[256], F fill) {
 
 // lml from y.alpha and sum log L_ii (R&W 2.30).
 __device__ inline double lml_value(double ya, double logdet, int m) { return -0.5 * ya - logdet - 0.5 * (double)m * LOG2PI; }
+
+// The leave-one-out quantities of sample i from its target, alpha_i and c_i = (K^-1)_ii (R&W 5.10 - 5.12): predictive mean
+// and variance, log predictive density, squared residual.
+struct LooSample {
+    double mean, var, logp, sq;
+};
+
+__device__ inline LooSample loo_sample(double yi, double al, double c) {
+    const double r = al / c, mean = yi - r, var = 1.0 / c, d = yi - mean;
+    return {mean, var, -0.5 * log(var) - d * d / (2.0 * var) - 0.5 * LOG2PI, r * r};
+}
+
+// loo_mse from the sum of the squared residuals.
+__device__ inline double loo_mse_value(double sq, int m) { return sq / (double)m; }
 
 }  // namespace evidence
 }  // namespace ital

@@ -10,9 +10,9 @@
 // The five leading launches are chain_prologue (evidence_chain.h), the host function ital_gp_evidence runs, and the reduction
 // adds y.alpha and sum log L_ii through the same serial_sums and lml_value: factor, alpha, inverse diagonal and lml have its
 // bits because they come from the same code.  The product is the 128 x 128 LDS-staged v_mfma_f64_16x16x4_f64 tile of
-// mfma_tile.h (its LDS layout and mfma_stage) with BOTH operands read k-major behind predicates (tile_tn below): M is stored
-// [k][i], W_ij = sum_k M[k][i] M[k][j] runs down its columns, and a run of 16 neighbouring columns of one row k is one
-// 128-byte read.  In the chain W never reaches memory: the epilogue turns a tile into two numbers.
+// mfma_tile.h (its LDS layout and mfma_stage) with BOTH operands read k-major behind predicates (tile_tn, evidence_chain.h):
+// M is stored [k][i], W_ij = sum_k M[k][i] M[k][j] runs down its columns, and a run of 16 neighbouring columns of one row k is
+// one 128-byte read.  In the chain W never reaches memory: the epilogue turns a tile into two numbers.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -57,43 +57,6 @@ __global__ __launch_bounds__(256, 2) void sqdist_lower_kernel(DistArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------- W = M^T M
-// acc[p][q] += sum over kbeg <= k < kend of A(k, r) B(k, c) for the 128 x 128 tile of a workgroup of 256 threads: wave
-// (wy, wx) owns tile rows 64 wy + 16 p + (kg + 4 reg) and tile columns 64 wx + 16 q + col (D layout of the f64 MFMA).
-// fa(k, r) / fb(k, c): the element of A at tile row r / of B at tile column c, both k-major; they return 0 outside their
-// operand (k at or past kend included).  Thread (k = tid / 16, tid % 16) stages eight runs of 16 columns of its k for each
-// operand, into the layout mfma_stage reads.  Register + LDS double buffer, one barrier per stage; ends with a barrier.
-template <class FA, class FB>
-__device__ inline void tile_tn(FA fa, FB fb, int kbeg, int kend, StageLds& lds, d4 acc[4][4]) {
-    const int kb = threadIdx.x >> 4, c16 = threadIdx.x & 15;
-    double ra[8], rb[8];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            ra[u] = fa(k0 + kb, c16 + 16 * u);
-            rb[u] = fb(k0 + kb, c16 + 16 * u);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            lds[buf][0][kb][c16 + 16 * u] = ra[u];
-            lds[buf][1][kb][c16 + 16 * u] = rb[u];
-        }
-    };
-    const int nstep = (kend - kbeg + KS - 1) / KS;
-    if (nstep <= 0) return;
-    fetch(kbeg);
-    stage(0);
-    __syncthreads();
-    for (int s_ = 0; s_ < nstep; s_++) {
-        const int buf = s_ & 1;
-        if (s_ + 1 < nstep) fetch(kbeg + (s_ + 1) * KS);
-        mfma_stage(lds, buf, acc);
-        if (s_ + 1 < nstep) stage(buf ^ 1);
-        __syncthreads();
-    }
-}
-
 struct ProdArgs {
     const double* M; int n; const int* info;       // inverse factor g at M + g n n, row stride n, lower triangle
     double* W; int64_t ldw;                        // stored form: W_g at W + g n ldw

@@ -733,7 +733,7 @@ class GaussianProcess(object):
         return self
 
     def _evidence_run(self, params_list, max_bytes, events, shapes, chunk_of, desc_cls, entry, workspace, n_events, outputs):
-        """What evidence() and evidence_grad() share: the candidates go through `entry` (descriptor `desc_cls`, workspace
+        """What evidence(), evidence_grad() and loo_grad() share: the candidates go through `entry` (descriptor `desc_cls`, workspace
         function `workspace`) in chunks of at most `chunk_of(max_bytes)`, with y, the parameters, the Grams, the workspace,
         info and a status word of the call's own on the device; `events` (`n_events` of them) reach the last chunk only.
         `shapes`: name -> shape of one candidate's entry of each returned float64 array; `ok` [G] bool is added.
@@ -854,6 +854,48 @@ class GaussianProcess(object):
         return self._evidence_run(params_list, max_bytes, events, dict(lml=(), grad=(3,)), self.evidence_grad_chunk,
                                   _lib.ItalEvidenceGradDesc, self._lib.ital_gp_evidence_grad,
                                   self._lib.ital_gp_evidence_grad_workspace, 8, outputs)
+
+    def loo_grad_chunk(self, max_bytes=1 << 30):
+        """Candidates loo_grad() sends to the device at once so that their Grams, workspace and outputs stay below `max_bytes`
+        (at most 65535, the limit of one ital_gp_loo_grad call); MemoryError if one candidate alone exceeds it.  The squared
+        distances are shared by the candidates of a chunk and counted once."""
+        m = self.m
+        one, two = (int(self._lib.ital_gp_loo_grad_workspace(m, c)) for c in (1, 2))
+        per = 8 * (m * m + (two - one) + 9)
+        shared = 8 * (2 * one - two)
+        if shared + per > max_bytes:
+            raise MemoryError("one candidate at m = %d takes %d bytes, more than max_bytes = %d" % (m, shared + per, max_bytes))
+        return int(min((max_bytes - shared) // per, 65535))
+
+    def loo_grad(self, params_list, *, max_bytes=1 << 30, events=None):
+        """The closed-form leave-one-out scores of hyper-parameter candidates on the model's own labelled set (queries
+        included) and their gradients in the LOGARITHMS of the parameters, without touching the model: for each dict of
+        `params_list` (`length_scale`, optional `var` / `noise`; default: the model's current value) the quantities of
+        include/ital_loo_grad.h.  Returns a dict of numpy arrays: `loo_logp`, `loo_mse` [G] (the bits evidence() returns),
+        `grad_logp`, `grad_mse` [G, 3] (d / d log length_scale, d log var, d log noise), `ok` [G] bool (the candidate's Gram
+        was positive definite; otherwise -inf, +inf and NaN rows).
+
+        Argument handling, chunking and errors are those of evidence_grad(): chunks whose Grams and workspace stay below
+        `max_bytes`, values that do not depend on the chunking; XT, XTn and y are read and only buffers of the call's own are
+        written -- L, alpha, V, mu, s2, the status word and both random streams stay as they are.  Every rank computes the same
+        thing locally: no collective.  RuntimeError for an unfitted model, ValueError for a non-positive length_scale / var,
+        MemoryError if one candidate alone exceeds max_bytes.
+        `events`: None, or nine recorded torch events that bracket the eight stages of the LAST chunk
+        (tools/loo_grad_bench.py)."""
+        def outputs(d, chunk):
+            values = torch.empty((chunk, 2), dtype=torch.float64, device=self.device)
+            grad = torch.empty((chunk, 2, 3), dtype=torch.float64, device=self.device)
+            d.values, d.grad = _ptr(values), _ptr(grad)
+
+            def download(out, g0, c):
+                v, g = values[:c].cpu().numpy(), grad[:c].cpu().numpy()
+                out["loo_logp"][g0:g0 + c], out["loo_mse"][g0:g0 + c] = v[:, 0], v[:, 1]
+                out["grad_logp"][g0:g0 + c], out["grad_mse"][g0:g0 + c] = g[:, 0], g[:, 1]
+            return download
+
+        return self._evidence_run(params_list, max_bytes, events, dict(loo_logp=(), loo_mse=(), grad_logp=(3,), grad_mse=(3,)),
+                                  self.loo_grad_chunk, _lib.ItalLooGradDesc, self._lib.ital_gp_loo_grad,
+                                  self._lib.ital_gp_loo_grad_workspace, 9, outputs)
 
     def check_status(self, status=None):
         """Raises if a kernel flagged a numerical failure.  `status`: the word as already downloaded (e.g. the OR over all

@@ -496,16 +496,19 @@ class ActiveRetrievalBase(object):
             self.set_params(**best)
         return best, score
 
-    def fit_params(self, params=tune.PARAM_NAMES, init=None, restarts=8, bounds=None, maxiter=100, apply=True, verbose=0):
+    def fit_params(self, params=tune.PARAM_NAMES, init=None, restarts=8, bounds=None, maxiter=100, apply=True, verbose=0,
+                   criterion='lml'):
         """Fits kernel hyper-parameters of a live session to its own labels by maximising the log marginal likelihood from
         its gradient on the device (tune.fit_session_params: L-BFGS-B over the logarithms of `params` from `restarts`
         deterministic starting points at once, restart 0 being `init` or the session's current values) and, with `apply`,
         makes them the session's (set_params).  The continuous counterpart of tune_params(), which only finds what lies on
-        its grid.  Returns (fitted parameters, their log marginal likelihood).  LinAlgError when no starting point has a
+        its grid.  `criterion`: 'lml', or 'loo_logp' / 'loo_mse', the leave-one-out scores of tune_params, climbed from
+        their gradients (GaussianProcess.loo_grad); 'loo_mse' fits at most one of var and noise.  Returns (fitted parameters,
+        their score: the log marginal likelihood, loo_logp or minus loo_mse).  LinAlgError when no starting point has a
         positive definite Gram; the session is then exactly as it was.  `rounds` and both random streams stay as they are.
         Several ranks: every rank makes the same call."""
         best, lml = tune.fit_session_params(self, params, init=init, restarts=restarts, bounds=bounds, maxiter=maxiter,
-                                            verbose=verbose)
+                                            verbose=verbose, criterion=criterion)
         if best is None:
             raise np.linalg.LinAlgError("no starting point has a positive definite kernel matrix of the labelled samples")
         if apply:

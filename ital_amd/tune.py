@@ -557,8 +557,12 @@ def session_starts(init, restarts=8, bounds=None, free=PARAM_NAMES):
     return np.array(rows)
 
 
+#: the criteria fit_session_params can climb: those of session_scores that have a gradient on the device
+FIT_CRITERIA = ('lml', 'loo_logp', 'loo_mse')
+
+
 def fit_session_params(gp_or_learner, params=PARAM_NAMES, init=None, restarts=8, bounds=None, maxiter=100, verbose=0,
-                       records=None):
+                       records=None, criterion='lml'):
     """Fits kernel hyper-parameters of a live session -- a GaussianProcess or a learner -- to its own labels by maximising the
     log marginal likelihood continuously, from its gradient on the device (GaussianProcess.evidence_grad,
     include/ital_evidence_grad.h): what GaussianProcessRegressor.fit does, and the other half of optimize_session_params,
@@ -570,9 +574,18 @@ def fit_session_params(gp_or_learner, params=PARAM_NAMES, init=None, restarts=8,
     them run in one L-BFGS-B iteration (maximize_lml), one device call per evaluation.  No random generator is touched.
     `verbose`: 1 prints the result, 2 every restart.  `records`: a list that receives maximize_lml's per-restart records.
     Returns (dict of the fitted values of `params`, their lml) -- what set_params() takes -- or (None, -inf) if no start has
-    a positive definite Gram."""
+    a positive definite Gram.
+
+    `criterion`: 'lml', or one of the closed-form leave-one-out scores of session_scores, 'loo_logp' and 'loo_mse', climbed
+    from GaussianProcess.loo_grad (include/ital_loo_grad.h) through the same maximize_lml; the score returned is then the
+    criterion's value in session_scores' orientation (minus the mse).  'loo_ap' has no gradient: ValueError, as for any other
+    name.  loo_mse does not change when var and noise are scaled together, so it fits at most one of them: ValueError."""
+    if criterion not in FIT_CRITERIA:
+        raise ValueError("criterion must be one of %s: %r has no gradient" % (', '.join(FIT_CRITERIA), criterion))
     gp = _session_gp(gp_or_learner)
     cols = _free_columns(params)
+    if criterion == 'loo_mse' and 1 in cols and 2 in cols:
+        raise ValueError('loo_mse does not change when var and noise are scaled together: fit at most one of var and noise')
     start = {'length_scale': gp.length_scale, 'var': gp.var, 'noise': gp.noise}
     unknown = set(init or {}) - set(PARAM_NAMES)
     if unknown:
@@ -587,8 +600,14 @@ def fit_session_params(gp_or_learner, params=PARAM_NAMES, init=None, restarts=8,
     starts = session_starts(start, restarts, bounds, params)
 
     def evaluate(theta):
-        ev = gp.evidence_grad([dict(zip(PARAM_NAMES, (float(v) for v in row))) for row in theta])
-        return ev['lml'], ev['grad'], ev['ok']
+        cands = [dict(zip(PARAM_NAMES, (float(v) for v in row))) for row in theta]
+        if criterion == 'lml':
+            ev = gp.evidence_grad(cands)
+            return ev['lml'], ev['grad'], ev['ok']
+        ev = gp.loo_grad(cands)
+        if criterion == 'loo_mse':
+            return -ev['loo_mse'], -ev['grad_mse'], ev['ok']
+        return ev['loo_logp'], ev['grad_logp'], ev['ok']
 
     best, lml, recs = maximize_lml(evaluate, starts, bounds, params, maxiter)
     if records is not None:
