@@ -6,6 +6,9 @@
 // One workgroup of 16 waves, one wave per new row (c <= 16) after the kernel values: tiny (m <= a few hundred), latency-bound, stays in L2 -- the
 // structure below keeps the number of dependent memory round trips per append at O(m / 64), not O(m).
 // The new feature rows must already sit in XT rows m..m+c-1 (with their squared norms in XTn).
+// Written: L rows [m, m+c), columns [0, m+c) (+0.0 above the diagonal of the new block), and alpha[m, m+c); nothing else.
+// Of rows < m only the lower triangle enters the arithmetic: their strict upper triangle inside the 64 x 64 diagonal blocks is
+// loaded along with the blocks and never used -- it may hold anything (NaN included) but must be readable memory of the matrix.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,11 +50,14 @@ __global__ __launch_bounds__(1024) void chol_append_kernel(const double* XT, con
         if (j < c) {
             const double* src = sa.rows + (int64_t)sa.lb.slot[j] * ldx;
             double* dst = sa.XT_w + (int64_t)j * ldx;
+            // summed in the order of row_norms_kernel (rbf.hip), as stage_labelled_kernel does: bounds and expression must stay
+            // textually the same in all three, so that the norms have the same bits (ldx is a multiple of 16: k + 1 < ldx)
             double acc = 0;
-            for (int k = lane; k < ldx; k += 64) {
-                const double v = src[k];
-                dst[k] = v;
-                acc += v * v;
+            for (int k = lane * 2; k < ldx; k += 128) {
+                const double2 v = {src[k], src[k + 1]};
+                dst[k] = v.x;
+                dst[k + 1] = v.y;
+                acc += v.x * v.x + v.y * v.y;
             }
             acc = wave_sum(acc);
             if (lane == 0) { sa.XTn_w[j] = acc; sa.y_w[j] = sa.lb.y[j]; }

@@ -35,7 +35,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void row_norms_kernel(const double* __restrict__ X, int64_t n, int ldx,
                                                         double* __restrict__ xnorm) {
-    // one wave per row, 16-B loads, wave reduction
+    // one wave per row, 16-B loads, wave reduction.  The staging kernels (stage_labelled_kernel below, chol_append_kernel)
+    // repeat this summation, expression for expression, so that their norms have the same bits: change all three together
     int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     int lane = threadIdx.x & 63;
     int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -242,11 +243,16 @@ __global__ __launch_bounds__(64) void stage_labelled_kernel(const double* __rest
     if (j >= lb.c) return;
     const double* src = rows + (int64_t)lb.slot[j] * ldx;
     double* dst = XT_dst + (int64_t)j * ldx;
+    // summed in the order of row_norms_kernel: a staged row's norm has the bits of that row's entry in xnorm.  The loop bounds
+    // and the expression `acc += v.x * v.x + v.y * v.y` must stay textually those of row_norms_kernel (and of the staging in
+    // chol_append_kernel), so that the compiler contracts all three alike; k + 1 < ldx because ldx is a multiple of 16
+    // (tests/test_gpu_gp_update.py compares the bits)
     double acc = 0;
-    for (int k = lane; k < ldx; k += 64) {
-        const double v = src[k];
-        dst[k] = v;
-        acc += v * v;
+    for (int k = lane * 2; k < ldx; k += 128) {
+        const double2 v = {src[k], src[k + 1]};
+        dst[k] = v.x;
+        dst[k + 1] = v.y;
+        acc += v.x * v.x + v.y * v.y;
     }
     acc = wave_sum(acc);
     if (lane == 0) { XTn_dst[j] = acc; y_dst[j] = lb.y[j]; }

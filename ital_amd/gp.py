@@ -166,6 +166,8 @@ class GaussianProcess(object):
         dev = self.device
         old = getattr(self, "cap", 0)
         V = torch.zeros((cap, self.ldv), dtype=torch.float64, device=dev)
+        # the kernels use the lower triangle only (ital_chol_append loads the strict upper triangle of the diagonal blocks
+        # without using it, csrc/chol.hip); the zeros there serve the host side (_factor, state_dict)
         L = torch.zeros((cap, cap), dtype=torch.float64, device=dev)
         alpha = torch.zeros(cap, dtype=torch.float64, device=dev)
         XT = torch.zeros((cap, self.ldx), dtype=torch.float64, device=dev)
