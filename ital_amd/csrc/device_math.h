@@ -17,8 +17,11 @@ namespace ital {
 // pair the register file spills; the compiler's v_fmac + v_mov_b64 form (coefficients parked in VGPRs) is the fastest.
 __device__ __forceinline__ double fma_k(double acc, double x, double K) { return fma(acc, x, K); }
 
-// n / d for well-scaled d (polynomial denominators, no zero / inf / subnormal): hardware reciprocal seed, two
-// Newton steps and one residual correction -- ~1 ulp, about half the instructions of the IEEE division expansion.
+// n / d for well-scaled d (polynomial denominators, no zero / inf / subnormal): hardware reciprocal seed, one Newton
+// step and one residual correction -- ~1 ulp, about half the instructions of the IEEE division expansion.
+// Cost on MI355X (tools/ubench/inst_rate.hip, per wave-instruction and SIMD): the seed 7.0 ns, as much as 3.5 simple
+// instructions, the five that follow 2.0 - 2.4 ns each -- about 18 ns per quotient, 7 of them the seed.  Chains that divide
+// at the same point of the program share the seed: fast_div_group below.
 __device__ __forceinline__ double fast_div(double n, double d) {
     // v_rcp_f64 is good to ~2^-23; one Newton step on the reciprocal (2^-46), then the residual correction of the quotient
     // squares the error once more: <= 1 ulp without a second step on the reciprocal
@@ -29,6 +32,66 @@ __device__ __forceinline__ double fast_div(double n, double d) {
     r = fma(fma(-d, r, 1.0), r, r);
     double q = n * r;
     return fma(fma(-d, q, n), r, q);
+}
+
+// n[k] / d[k] for the first `len` of GM independent pairs with ONE reciprocal seed: v_rcp_f64 is the most expensive
+// instruction of fast_div (7.0 ns against 2.0 - 2.4 ns for a multiplication or an FMA on MI355X), and chains that divide at
+// the same point of the program can share it -- prefix products of the denominators, the seed and its Newton step on the
+// product of all, then each reciprocal by back-substitution: 3 (len - 1) multiplications instead of len - 1 seeds and
+// 2 (len - 1) FMAs.  The recovered reciprocals carry the Newton step's 2^-46 plus a few roundings; the residual correction
+// per quotient is fast_div's own and squares that error, so the quotients are fast_div's (checked over 1.2e7 random pairs
+// per range by tools/batch_div_check.cpp: equal in every case, both within 0.5 ulp of the long-double quotient).
+// The product must stay in range: here at most six factors from [0.0022, 1.5e10].  A non-finite or zero denominator
+// reaches every quotient of its group, so a group holds only chains whose values are added up together anyway.
+// len, GM: compile-time constants after unrolling; len == 1 is fast_div itself.
+template <int GM>
+__device__ __forceinline__ void fast_div_group(const double (&n)[GM], const double (&d)[GM], double (&out)[GM], int len) {
+    if (len == 1) {
+        out[0] = fast_div(n[0], d[0]);
+        return;
+    }
+    double pre[GM], r[GM];
+    pre[0] = d[0];
+#pragma unroll
+    for (int k = 1; k < GM; k++)
+        if (k < len) pre[k] = pre[k - 1] * d[k];
+    const double dall = pre[len - 1];
+    double ra = __builtin_amdgcn_rcp(dall);
+#ifdef ITAL_DIV_TWO_STEPS
+    ra = fma(fma(-dall, ra, 1.0), ra, ra);
+#endif
+    ra = fma(fma(-dall, ra, 1.0), ra, ra);
+#pragma unroll
+    for (int k = GM - 1; k >= 1; k--)
+        if (k < len) {
+            r[k] = ra * pre[k - 1];     // 1 / d[k] = (1 / (d[0] .. d[k])) (d[0] .. d[k-1])
+            ra = ra * d[k];             // 1 / (d[0] .. d[k-1])
+        }
+    r[0] = ra;
+#pragma unroll
+    for (int k = 0; k < GM; k++)
+        if (k < len) {
+            const double q = n[k] * r[k];
+            out[k] = fma(fma(-d[k], q, n[k]), r[k], q);
+        }
+}
+
+// N independent quotients in groups of G (the last group takes what is left); G <= 1: N times fast_div.
+template <int N, int G>
+__device__ __forceinline__ void fast_div_batch(const double (&n)[N], const double (&d)[N], double (&out)[N]) {
+    constexpr int GM = G > 1 ? G : 1;
+#pragma unroll
+    for (int g0 = 0; g0 < N; g0 += GM) {
+        double gn[GM], gd[GM], go[GM];
+        const int len = N - g0 < GM ? N - g0 : GM;
+#pragma unroll
+        for (int k = 0; k < GM; k++)
+            if (k < len) { gn[k] = n[g0 + k]; gd[k] = d[g0 + k]; }
+        fast_div_group<GM>(gn, gd, go, len);
+#pragma unroll
+        for (int k = 0; k < GM; k++)
+            if (k < len) out[g0 + k] = go[k];
+    }
 }
 
 // Polynomial coefficients as operands.  With literals (LitK) the compiler materialises every coefficient next to its use:
@@ -277,12 +340,18 @@ __device__ __forceinline__ double sqrt_pos(double a) {
 // absolute difference to MVNPHI below 5e-21 (Phi(z) for z > 0 is 1 - p: unchanged to the last bit).  The reference adds
 // eps = 1e-12 to every probability before its logarithms (ital.py:208-222).  In a wave of 64 chains some |z| lies beyond
 // the cut-off often enough that the branch cost 3.5 % (t = 4) to 4.6 % (t = 8) of the lattice sums.
-template <class K, bool CF = true>
-__device__ __forceinline__ double mvn_phi(double z, const K& kk) {
+// Hart's rational P(|z|) / Q(|z|) as numerator and denominator (Q in [440, 1.42e10] on |z| <= 37).
+__device__ __forceinline__ void hart_pq(double zabs, double& num, double& den) {
     const double P0 = 220.2068679123761, P1 = 221.2135961699311, P2 = 112.0792914978709, P3 = 33.91286607838300,
                  P4 = 6.373962203531650, P5 = .7003830644436881, P6 = .03526249659989109;
     const double Q0 = 440.4137358247522, Q1 = 793.8265125199484, Q2 = 637.3336333788311, Q3 = 296.5642487796737,
                  Q4 = 86.78073220294608, Q5 = 16.06417757920695, Q6 = 1.755667163182642, Q7 = .08838834764831844;
+    num = fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(P6, zabs, P5), zabs, P4), zabs, P3), zabs, P2), zabs, P1), zabs, P0);
+    den = fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(Q7, zabs, Q6), zabs, Q5), zabs, Q4), zabs, Q3), zabs, Q2), zabs, Q1), zabs, Q0);
+}
+
+template <class K, bool CF = true>
+__device__ __forceinline__ double mvn_phi(double z, const K& kk) {
     const double ROOTPI = 2.506628274631001, CUTOFF = 7.071067811865475;
     const double zabs = fabs(z);
     double p;
@@ -291,8 +360,8 @@ __device__ __forceinline__ double mvn_phi(double z, const K& kk) {
     } else {
         const double expntl = exp_neg(-zabs * zabs / 2, kk);
         if (!CF || zabs < CUTOFF) {
-            const double num = fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(P6, zabs, P5), zabs, P4), zabs, P3), zabs, P2), zabs, P1), zabs, P0);
-            const double den = fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(Q7, zabs, Q6), zabs, Q5), zabs, Q4), zabs, Q3), zabs, Q2), zabs, Q1), zabs, Q0);
+            double num, den;
+            hart_pq(zabs, num, den);
             p = fast_div(expntl * num, den);
         } else {
             const double n5 = zabs + 0.65;
@@ -326,6 +395,27 @@ struct WithCF : K {};
 template <class K>
 __device__ __forceinline__ double mvn_phi_lat(double z, const WithCF<K>& kk) { return mvn_phi<K, true>(z, static_cast<const K&>(kk)); }
 
+// mvn_phi's rational form (CF = false) split around its division, for chains that share a reciprocal seed (fast_div_group):
+// with q = n / d formed by fast_div's arithmetic, mvn_phi_finish(z, q) is mvn_phi(z) bit for bit.
+// The denominator is Q(min(|z|, 37)): the same value on |z| <= 37, and finite -- Q(37) = 1.42e10 -- for every other z, a NaN
+// included, so that no chain can spoil the product its group takes the seed of.  The numerator keeps |z| itself: beyond 37 it
+// may be anything (the quotient is replaced by 0, as in mvn_phi), and a NaN z still gives a NaN Phi -- its own, not its
+// neighbours'.  One v_min_f64 per chain.  (Measured and rejected, docs/HISTORY.md: numerator 0 over denominator 1 chosen by
+// selects, and a wave-uniform branch to the unbatched form where any |z| > 37 -- both cost more than the seeds they save.)
+template <class K>
+__device__ __forceinline__ void mvn_phi_nd(double z, const K& kk, double& n, double& d) {
+    const double zabs = fabs(z);
+    const double expntl = exp_neg(-zabs * zabs / 2, kk);
+    double num, unused;
+    hart_pq(zabs, num, unused);
+    hart_pq(fmin(zabs, 37.0), unused, d);
+    n = expntl * num;
+}
+__device__ __forceinline__ double mvn_phi_finish(double z, double q) {
+    const double p = fabs(z) > 37.0 ? 0.0 : q;
+    return z > 0 ? 1 - p : p;
+}
+
 #ifndef ITAL_TAIL_LIT_S
 #define ITAL_TAIL_LIT_S 1     // coefficients of the Phi^-1 tail branch as in-place scalars (lit_s above)
 #endif
@@ -340,7 +430,9 @@ __device__ __forceinline__ double mvn_phi_lat(double z, const WithCF<K>& kk) { r
 __device__ __forceinline__ bool phinv_is_central(double p) { return fabs(p - 0.5) <= 0.425; }
 
 // central branch on q = p - 1/2 (bit-identical to AS241's (2p - 1)/2: doubling and halving are exact)
-__device__ __forceinline__ double phinv_central_q(double q) {
+// (numerator and denominator: phinv_central_q(q) = fast_div(n, d).  d lies in [1, 94] on |q| <= 0.425, and in [0.0022, 1]
+// -- never zero -- for the tail arguments 0.425 < |q| <= 0.5 whose quotient is discarded)
+__device__ __forceinline__ void phinv_central_nd(double q, double& n, double& d) {
     const double A0 = 3.3871328727963666080E0, A1 = 1.3314166789178437745E+2, A2 = 1.9715909503065514427E+3,
                  A3 = 1.3731693765509461125E+4, A4 = 4.5921953931549871457E+4, A5 = 6.7265770927008700853E+4,
                  A6 = 3.3430575583588128105E+4, A7 = 2.5090809287301226727E+3, B1 = 4.2313330701600911252E+1,
@@ -348,8 +440,14 @@ __device__ __forceinline__ double phinv_central_q(double q) {
                  B5 = 3.9307895800092710610E+4, B6 = 2.8729085735721942674E+4, B7 = 5.2264952788528545610E+3;
     const double r = 0.180625 - q * q;
     const double num = fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(A7, r, A6), r, A5), r, A4), r, A3), r, A2), r, A1), r, A0);
-    const double den = fma(fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(B7, r, B6), r, B5), r, B4), r, B3), r, B2), r, B1), r, 1.0);
-    return fast_div(q * num, den);
+    d = fma(fma_k(fma_k(fma_k(fma_k(fma_k(fma_k(B7, r, B6), r, B5), r, B4), r, B3), r, B2), r, B1), r, 1.0);
+    n = q * num;
+}
+
+__device__ __forceinline__ double phinv_central_q(double q) {
+    double n, d;
+    phinv_central_nd(q, n, d);
+    return fast_div(n, d);
 }
 
 __device__ __forceinline__ double phinv_central(double p) { return phinv_central_q(p - 0.5); }

@@ -60,24 +60,55 @@ __device__ __forceinline__ void flip_width(double (&w)[NCB], bool flipped) {
 // expensive log/sqrt branch runs on full waves of tail arguments only (typically once per 256 inversions instead of
 // once per 64).
 // q: wave-private LDS queue of 64*NC doubles.
-template <int NC, class K, int GRP = 0>
+// BG > 1: the central rationals of BG consecutive chains share one reciprocal seed (device_math.h fast_div_group) -- the same
+// quotients.  The NC chains of a lane must then belong to ONE sum: a chain with a NaN argument makes its group's values NaN.
+// A switch per call site: the re-computation in the reference's own summation order (qmc_exact.h) keeps BG = 0.
+template <int NC, class K, int GRP = 0, int BG = 0>
 __device__ __forceinline__ void phinv_wave(const double (&p)[NC], double (&out)[NC], double* __restrict__ q, int lane,
                                            const K& kk) {
     bool need[NC];
     int slot[NC];
     int total = 0;
+    if constexpr (BG > 1) {
+        static_assert(GRP == 0 || GRP % BG == 0, "a seed group must not straddle a scheduling group");
 #pragma unroll
-    for (int c = 0; c < NC; c++) {
-        // GRP > 0: the chains are evaluated in groups of GRP -- the scheduler may interleave the rationals of a group, not of
-        // all NC chains (whose temporaries would all be live at once: eval_chains_big)
-        if (GRP > 0 && c > 0 && c % GRP == 0) __builtin_amdgcn_sched_barrier(0);
-        const double qc = p[c] - 0.5;
-        need[c] = !(fabs(qc) <= 0.425);
-        out[c] = phinv_central_q(qc);   // garbage (never a trap) for tail arguments: replaced below
-        const unsigned long long m = __ballot(need[c]);
-        slot[c] = total + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        total += __popcll(m);
-        if (need[c]) q[slot[c]] = p[c];
+        for (int g0 = 0; g0 < NC; g0 += BG) {
+            if (GRP > 0 && g0 > 0 && g0 % GRP == 0) __builtin_amdgcn_sched_barrier(0);
+            const int len = NC - g0 < BG ? NC - g0 : BG;
+            double gn[BG], gd[BG], go[BG];
+#pragma unroll
+            for (int k = 0; k < BG; k++)
+                if (k < len) {
+                    const double qc = p[g0 + k] - 0.5;
+                    need[g0 + k] = !(fabs(qc) <= 0.425);
+                    phinv_central_nd(qc, gn[k], gd[k]);
+                }
+            fast_div_group<BG>(gn, gd, go, len);   // garbage (never a trap) for tail arguments: replaced below
+#pragma unroll
+            for (int k = 0; k < BG; k++)
+                if (k < len) {
+                    const int c = g0 + k;
+                    out[c] = go[k];
+                    const unsigned long long m = __ballot(need[c]);
+                    slot[c] = total + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    total += __popcll(m);
+                    if (need[c]) q[slot[c]] = p[c];
+                }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            // GRP > 0: the chains are evaluated in groups of GRP -- the scheduler may interleave the rationals of a group, not
+            // of all NC chains (whose temporaries would all be live at once: eval_chains_big)
+            if (GRP > 0 && c > 0 && c % GRP == 0) __builtin_amdgcn_sched_barrier(0);
+            const double qc = p[c] - 0.5;
+            need[c] = !(fabs(qc) <= 0.425);
+            out[c] = phinv_central_q(qc);   // garbage (never a trap) for tail arguments: replaced below
+            const unsigned long long m = __ballot(need[c]);
+            slot[c] = total + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            total += __popcll(m);
+            if (need[c]) q[slot[c]] = p[c];
+        }
     }
     if (total == 0) return;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -100,11 +131,43 @@ __device__ __forceinline__ void phinv_wave(const double (&p)[NC], double (&out)[
     phinv_wave<NC>(p, out, q, lane, LitK());
 }
 
+// Phi of stage i's conditioned limit for the NCB chains of a lane, BG consecutive chains sharing one reciprocal seed
+// (device_math.h fast_div_group / mvn_phi_nd): the values of mvn_phi_lat, bit for bit.  One group's numerators and
+// denominators are formed and divided before the next group's (a scheduling barrier between the groups).
+// The chains of a lane belong to ONE record's sum.  mvn_phi_nd keeps every denominator finite, so here not even a NaN limit
+// reaches the chain's neighbours; in phinv_wave it does, and there that sum is NaN either way.
+template <int NCB, int ND, int NCF, int BG, class K>
+__device__ __forceinline__ void phi_lat_grouped(const double (&yy)[NCB][ND], const double (&cf)[NCF], int i, double lmi,
+                                                const K& kk, double (&ph)[NCB]) {
+    static_assert(BG > 1 && ITAL_LATTICE_PHI_CF == 0, "the shared seed is written for the rational form of MVNPHI");
+#pragma unroll
+    for (int g0 = 0; g0 < NCB; g0 += BG) {
+        if (g0 > 0) __builtin_amdgcn_sched_barrier(0);
+        const int len = NCB - g0 < BG ? NCB - g0 : BG;
+        double z[BG], gn[BG], gd[BG], go[BG];
+#pragma unroll
+        for (int k = 0; k < BG; k++)
+            if (k < len) {
+                double sc = 0;
+#pragma unroll
+                for (int j = 0; j < i; j++) sc = fma(cf[i * (i - 1) / 2 + j], yy[g0 + k][j], sc);
+                z[k] = lmi - sc;
+                mvn_phi_nd(z[k], kk, gn[k], gd[k]);
+            }
+        fast_div_group<BG>(gn, gd, go, len);
+#pragma unroll
+        for (int k = 0; k < BG; k++)
+            if (k < len) ph[g0 + k] = mvn_phi_finish(z[k], go[k]);
+    }
+}
+
 // The integrand of NCB lattice points per lane (MVNDFN for one-sided limits): sequential conditioning over the T
 // variables, every chain independent of the others; returns the lane's sum of the integrand values.  cf: packed strict
 // lower triangle of the row-scaled factor, lm: scaled limits (wave-uniform), bit i of infi: variable i is bounded below.
 // FL: the call is in the all-upper form (ITAL_QMC_FLIP); bit i of infi then marks the variables that entered negated.
-template <int T, int NCB, class K, bool FL = false>
+// BPHI / BINV > 1: Phi / the central Phi^-1 of that many consecutive chains share one reciprocal seed (phi_lat_grouped,
+// phinv_wave): the same values, fewer v_rcp_f64.  0: every chain divides on its own.
+template <int T, int NCB, class K, bool FL = false, int BPHI = 0, int BINV = 0>
 __device__ __forceinline__ double eval_chains(const double (&xx)[NCB][(T - 1 > 0 ? T - 1 : 1)], bool (&dead)[NCB],
                                               const double (&cf)[(T * (T - 1) / 2 > 0 ? T * (T - 1) / 2 : 1)],
                                               const double (&lm)[T], unsigned infi_c, double* tailq, int lane, const K& kk) {
@@ -117,12 +180,16 @@ __device__ __forceinline__ double eval_chains(const double (&xx)[NCB][(T - 1 > 0
     for (int i = 0; i < T; i++) {
         const bool lower = (infi_c >> i) & 1u;
         double pin[NCB], ph[NCB];
+        if constexpr (BPHI > 1) {
+            phi_lat_grouped<NCB, (T - 1 > 0 ? T - 1 : 1), (T * (T - 1) / 2 > 0 ? T * (T - 1) / 2 : 1), BPHI>(yy, cf, i, lm[i], kk, ph);
+        } else {
 #pragma unroll
-        for (int c = 0; c < NCB; c++) {
-            double sc = 0;
+            for (int c = 0; c < NCB; c++) {
+                double sc = 0;
 #pragma unroll
-            for (int j = 0; j < i; j++) sc = fma(cf[i * (i - 1) / 2 + j], yy[c][j], sc);
-            ph[c] = mvn_phi_lat(lm[i] - sc, kk);
+                for (int j = 0; j < i; j++) sc = fma(cf[i * (i - 1) / 2 + j], yy[c][j], sc);
+                ph[c] = mvn_phi_lat(lm[i] - sc, kk);
+            }
         }
         if (FL) flip_width<NCB>(ph, lower);
 #pragma unroll
@@ -135,7 +202,7 @@ __device__ __forceinline__ double eval_chains(const double (&xx)[NCB][(T - 1 > 0
         }
         if (i < T - 1) {
             double out[NCB];
-            phinv_wave<NCB>(pin, out, tailq, lane, kk);
+            phinv_wave<NCB, K, 0, BINV>(pin, out, tailq, lane, kk);
 #pragma unroll
             for (int c = 0; c < NCB; c++) yy[c][i] = out[c];
         }
@@ -149,7 +216,7 @@ __device__ __forceinline__ double eval_chains(const double (&xx)[NCB][(T - 1 > 0
 // Sum over this lane's share of the 16 P lattice points of one orthant call of compile-time dimension T (8 randomly
 // shifted Korobov lattices of P points, each point with its antithetic partner).  lat: [8][NDIM] permuted generators, then
 // [8][NDIM] shifts; cf / lm / infi as eval_chains.  The caller adds the lanes up and divides by 16 P.
-template <int T, class K = LitK, int NH_ = ITAL_QMC_NH, bool FL = false>
+template <int T, class K = LitK, int NH_ = ITAL_QMC_NH, bool FL = false, int BPHI = 0, int BINV = 0>
 __device__ __forceinline__ double qmc_lane_sum(const double* __restrict__ lat,
                                                const double (&cf)[(T * (T - 1) / 2 > 0 ? T * (T - 1) / 2 : 1)],
                                                const double (&lm)[T], unsigned infi_c, double* __restrict__ tailq, int lane,
@@ -184,7 +251,7 @@ __device__ __forceinline__ double qmc_lane_sum(const double* __restrict__ lat,
             }
             dead[2 * h] = dead[2 * h + 1] = !ok;
         }
-        acc += eval_chains<T, NC, K, FL>(xx, dead, cf, lm, infi_c, tailq, lane, kk);
+        acc += eval_chains<T, NC, K, FL, BPHI, BINV>(xx, dead, cf, lm, infi_c, tailq, lane, kk);
     }
     if (NCL > 0 && NCL != NC) {
         constexpr int NCLA = NCL > 0 ? NCL : 1;
@@ -222,7 +289,7 @@ __device__ __forceinline__ double qmc_lane_sum(const double* __restrict__ lat,
             }
             dead[NCLA - 1] = !ok;
         }
-        acc += eval_chains<T, NCLA, K, FL>(xx, dead, cf, lm, infi_c, tailq, lane, kk);
+        acc += eval_chains<T, NCLA, K, FL, BPHI, BINV>(xx, dead, cf, lm, infi_c, tailq, lane, kk);
     }
     return acc;
 }

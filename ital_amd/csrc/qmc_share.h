@@ -23,7 +23,8 @@ struct QmcRounds {
 
 // eval_chains (all-upper form) with the first variable's interval width given: it does not depend on the lattice point, and
 // the round of the left-over chains has formed it already (w0: wave-uniform, flip_width applied).
-template <int T, int NCB, class K>
+// BPHI / BINV: seed groups of Phi and of the central Phi^-1 (eval_chains).
+template <int T, int NCB, class K, int BPHI = 0, int BINV = 0>
 __device__ __forceinline__ double eval_chains_w0(const double (&xx)[NCB][(T - 1 > 0 ? T - 1 : 1)], double w0,
                                                  const double (&cf)[(T * (T - 1) / 2 > 0 ? T * (T - 1) / 2 : 1)],
                                                  const double (&lm)[T], unsigned infi_c, double* tailq, int lane, const K& kk) {
@@ -34,15 +35,20 @@ __device__ __forceinline__ double eval_chains_w0(const double (&xx)[NCB][(T - 1 
     for (int i = 0; i < T; i++) {
         const bool lower = (infi_c >> i) & 1u;
         double pin[NCB], ph[NCB];
+        if (BPHI > 1 && i > 0) {
+            if constexpr (BPHI > 1)
+                phi_lat_grouped<NCB, (T - 1 > 0 ? T - 1 : 1), (T * (T - 1) / 2 > 0 ? T * (T - 1) / 2 : 1), BPHI>(yy, cf, i, lm[i], kk, ph);
+        } else {
 #pragma unroll
-        for (int c = 0; c < NCB; c++) {
-            if (i == 0) {
-                ph[c] = w0;
-            } else {
-                double sc = 0;
+            for (int c = 0; c < NCB; c++) {
+                if (i == 0) {
+                    ph[c] = w0;
+                } else {
+                    double sc = 0;
 #pragma unroll
-                for (int j = 0; j < i; j++) sc = fma(cf[i * (i - 1) / 2 + j], yy[c][j], sc);
-                ph[c] = mvn_phi_lat(lm[i] - sc, kk);
+                    for (int j = 0; j < i; j++) sc = fma(cf[i * (i - 1) / 2 + j], yy[c][j], sc);
+                    ph[c] = mvn_phi_lat(lm[i] - sc, kk);
+                }
             }
         }
         if (i > 0) flip_width<NCB>(ph, lower);
@@ -55,7 +61,7 @@ __device__ __forceinline__ double eval_chains_w0(const double (&xx)[NCB][(T - 1 
         }
         if (i < T - 1) {
             double out[NCB];
-            phinv_wave<NCB>(pin, out, tailq, lane, kk);
+            phinv_wave<NCB, K, 0, BINV>(pin, out, tailq, lane, kk);
 #pragma unroll
             for (int c = 0; c < NCB; c++) yy[c][i] = out[c];
         }
@@ -67,7 +73,7 @@ __device__ __forceinline__ double eval_chains_w0(const double (&xx)[NCB][(T - 1 
 }
 
 // qmc_lane_sum without its left-over round: the lane's sum over the FULL rounds of 2 NH chains.
-template <int T, class K, int NH>
+template <int T, class K, int NH, int BPHI = 0, int BINV = 0>
 __device__ __forceinline__ double qmc_lane_sum_full(const double* __restrict__ lat, double w0,
                                                     const double (&cf)[(T * (T - 1) / 2 > 0 ? T * (T - 1) / 2 : 1)],
                                                     const double (&lm)[T], unsigned infi_c, double* __restrict__ tailq, int lane,
@@ -90,7 +96,7 @@ __device__ __forceinline__ double qmc_lane_sum_full(const double* __restrict__ l
                 xx[2 * h + 1][j] = 1 - xx[2 * h][j];
             }
         }
-        acc += eval_chains_w0<T, NC, K>(xx, w0, cf, lm, infi_c, tailq, lane, kk);
+        acc += eval_chains_w0<T, NC, K, BPHI, BINV>(xx, w0, cf, lm, infi_c, tailq, lane, kk);
     }
     return acc;
 }

@@ -96,6 +96,24 @@
 // slots of the three waves that retire early are not refilled before the workgroup ends (resident wave-cycles -28 %).
 #define ITAL_QMC_SHARE_LAST 1
 #endif
+#ifndef ITAL_QMC_BATCH_DIV
+// The chains of a lane share reciprocal seeds where they divide at the same point of the program (device_math.h
+// fast_div_group): Hart's rational in Phi (ITAL_QMC_BATCH_PHI(T) chains per seed) and AS241's central rational in Phi^-1
+// (ITAL_QMC_BATCH_PHINV(T)); 0 or 1: every chain its own seed.  ITAL_QMC_BATCH_DIV=0 compiles to the unbatched loops.
+// Three chains per seed in both divisions at t = 3 and t = 4: what the register file takes without scratch at four waves per
+// SIMD (six per seed spill: 28 B at t = 4 in Phi^-1 alone, 60 / 92 B in Phi).  Same quotients, same sums bit for bit.
+// Measured (9298 x 256, k = 4, same box, A B A B, eight runs each, profiles/batch_div_*): the round 2.3308 -> 2.2696 ms,
+// qmc_main_kernel<4> 1.681 -> 1.632 ms; nearly all of it at t = 4.  t >= 5 (0): not wired into eval_items_ps, not measured.
+// docs/HISTORY.md, "one reciprocal seed for a lane's chains": the resource table, the per-site variants, the forms of Phi's
+// division that were measured and dropped.
+#define ITAL_QMC_BATCH_DIV 1
+#endif
+#ifndef ITAL_QMC_BATCH_PHINV
+#define ITAL_QMC_BATCH_PHINV(T) ((T) <= 4 ? 3 : 0)
+#endif
+#ifndef ITAL_QMC_BATCH_PHI
+#define ITAL_QMC_BATCH_PHI(T) ((T) <= 4 ? 3 : 0)
+#endif
 #ifndef ITAL_QMC_SHARE_RECS
 #define ITAL_QMC_SHARE_RECS 4   // records per wave where the left-over chains are shared (4 x 16 chains: a full wave)
 #endif
@@ -268,6 +286,9 @@ struct Qmc {
     static constexpr int PREP_THREADS = T <= 6 ? 256 : 128;
     // lattice items per lane and round of the lattice-sum kernel (each with its antithetic partner), see ITAL_QMC_MAIN_NH
     static constexpr int NH = ITAL_QMC_MAIN_NH(T);
+    // chains per reciprocal seed in Phi / the central Phi^-1 (the rational form of MVNPHI only), see ITAL_QMC_BATCH_DIV
+    static constexpr int BPHI = ITAL_QMC_BATCH_DIV && !ITAL_LATTICE_PHI_CF ? ITAL_QMC_BATCH_PHI(T) : 0;
+    static constexpr int BINV = ITAL_QMC_BATCH_DIV ? ITAL_QMC_BATCH_PHINV(T) : 0;
     static constexpr int TAILQ = 128 * NH;                    // compaction queue of the Phi^-1 tail branch (in place)
     static constexpr bool PS = ITAL_QMC_MAIN_PS(T), CFL = PS && ITAL_QMC_MAIN_CFL(T);
     // a wave takes RPW consecutive records (sign patterns of one candidate) and evaluates their left-over chains in one round
@@ -643,7 +664,7 @@ __device__ __forceinline__ void qmc_main_shared(const uint8_t* __restrict__ aliv
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const double w0 = lastv[64 + Q::RPW + j];      // (a vector value, for the same reason)
-            const double part = qmc_lane_sum_full<T, typename Q::Coef, Q::NH>(lat, w0, cf, lm, flips, tailq, ln, kk);
+            const double part = qmc_lane_sum_full<T, typename Q::Coef, Q::NH, Q::BPHI, Q::BINV>(lat, w0, cf, lm, flips, tailq, ln, kk);
             __asm__ volatile("" : "+v"(jv));
             const int j2 = __builtin_amdgcn_readfirstlane(jv);
             const double acc = part + (ln < 16 ? lastv[16 * j2 + ln] : 0.0);
@@ -726,7 +747,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ITAL_QMC_WA
         kk.load();
         constexpr bool FL = ITAL_QMC_FLIP != 0;
         const double acc = Q::PS ? qmc_lane_sum_ps<T, typename Q::Coef, Q::NH, Q::CFL, FL>(lat, cf, lm, slab, infi, tailq, lane, kk)
-                                 : qmc_lane_sum<T, typename Q::Coef, Q::NH, FL>(lat, cf, lm, infi, tailq, lane, kk);
+                                 : qmc_lane_sum<T, typename Q::Coef, Q::NH, FL, Q::BPHI, Q::BINV>(lat, cf, lm, infi, tailq, lane, kk);
 #else
         const double acc = qmc_lane_sum<T, LitK, Q::NH, ITAL_QMC_FLIP != 0>(lat, cf, lm, infi, tailq, lane);
 #endif
