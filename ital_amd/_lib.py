@@ -317,6 +317,16 @@ COMPACT_SIGNATURES = {
 }
 
 
+#: a live session in a context (reserve / add_rows / remove_rows / set_params / evidence), declared in include/ital_ctx_live.h
+CTX_LIVE_SIGNATURES = {
+    "ital_ctx_reserve": (c_int, [c_void_p, c_int, c_void_p]),
+    "ital_ctx_add_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "ital_ctx_remove_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ital_ctx_set_params": (c_int, [c_void_p, c_double, c_double, c_double, c_void_p]),
+    "ital_ctx_evidence": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -338,7 +348,8 @@ def load(path=LIB_PATH):
     for name, (res, args) in list(SIGNATURES.items()) + list(CTX_SIGNATURES.items()) + list(DENSE_SIGNATURES.items()) + \
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-            list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()):
+            list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
+            list(CTX_LIVE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args
