@@ -20,7 +20,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <initializer_list>
 #include <unordered_map>
 #include <vector>
 
@@ -42,12 +41,37 @@ int owner_of(const ital_ctx* c, int64_t gi) {
     return owner;
 }
 
+// All unlabelled samples, ascending: the candidate list of a fetch that is given none.
+std::vector<int64_t> unlabelled(const ital_ctx* c) {
+    std::vector<int64_t> list;
+    list.reserve((size_t)(c->n_total - c->n_seen));
+    for (int64_t i = 0; i < c->n_total; i++)
+        if (!c->seen[(size_t)i]) list.push_back(i);
+    return list;
+}
+
+// The device status word, read and written by blocking copies.
+int read_status(const ital_ctx* c, int* s) {
+    return hipMemcpy(s, c->status, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess ? 0 : ital_fail(-5, "ital_ctx_fetch: stream error");
+}
+int write_status(ital_ctx* c, int s) {
+    return hipMemcpy(c->status, &s, sizeof(int), hipMemcpyHostToDevice) == hipSuccess ? 0 : ital_fail(-5, "ital_ctx_fetch: stream error");
+}
+
+// A host table into a buffer of its own, by a blocking copy (the stream tables: made once per context).
+template <class T>
+int upload_table(DevBuf<T>& buf, const std::vector<T>& host) {
+    if (!buf.alloc((int64_t)host.size())) return ital_fail(-12, "ital_ctx_fetch: out of device memory");
+    if (hipMemcpy(buf, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+        return ital_fail(-5, "ital_ctx_fetch: upload of the stream tables failed");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ital_ctx_destroy(ital_ctx* c) {
     if (!c) return 0;
     (void)hipDeviceSynchronize();
-    for (void* p : c->owned) (void)hipFree(p);
     delete c;
     return 0;
 }
@@ -70,42 +94,12 @@ extern "C" int ital_ctx_create(int64_t n_total, int d, double length_scale, doub
     c->cap = pad16(capacity > 0 ? capacity : 256);
     c->length_scale = length_scale; c->var = var; c->noise = noise;
     c->rank = rank; c->world = world; c->comm = nccl_comm;
-    const int kmax = c->kmax, ldx = c->ldx, cap = c->cap;
-    const int rec_len = ital_record_len(ldx, cap, kmax);
-    c->X = dalloc<double>(c, (size_t)std::max<int64_t>(c->n, 1) * ldx);
-    c->xn = dalloc<double>(c, std::max<int64_t>(c->n, 1));
-    c->L = dalloc<double>(c, (size_t)cap * cap);
-    c->alpha = dalloc<double>(c, cap);
-    c->XT = dalloc<double>(c, (size_t)cap * ldx);
-    c->XTn = dalloc<double>(c, cap);
-    c->V = dalloc<double>(c, (size_t)cap * c->ldv);
-    c->mu = dalloc<double>(c, c->ldv);
-    c->s2 = dalloc<double>(c, c->ldv);
-    c->ybuf = dalloc<double>(c, 16);
-    c->status = dalloc<int>(c, 1);
-    c->C = dalloc<double>(c, (size_t)kmax * c->ldv);
-    c->ret = dalloc<int64_t>(c, kmax + 1);
-    c->rec = dalloc<double>(c, rec_len);
-    c->rec_all = dalloc<double>(c, (size_t)world * rec_len);
-    c->work3k = dalloc<double>(c, 3 * 1024);
-    c->batch.kmax = kmax; c->batch.ldx = ldx; c->batch.ldw = cap;
-    c->batch.bidx = dalloc<int64_t>(c, kmax);
-    c->batch.bgpos = dalloc<int64_t>(c, kmax);
-    c->batch.bsort = dalloc<int32_t>(c, kmax);
-    c->batch.bmu = dalloc<double>(c, kmax);
-    c->batch.sig = dalloc<double>(c, (size_t)kmax * kmax);
-    c->batch.XB = dalloc<double>(c, (size_t)kmax * ldx);
-    c->batch.XBn = dalloc<double>(c, kmax);
-    c->batch.VB = dalloc<double>(c, (size_t)kmax * cap);
-    // every allocation (an unchecked failure would surface as a device fault in the first kernel that touches the buffer)
-    const void* all[] = {c->X, c->xn, c->L, c->alpha, c->XT, c->XTn, c->V, c->mu, c->s2, c->ybuf, c->status, c->C, c->ret, c->rec,
-                         c->rec_all, c->work3k, c->batch.bidx, c->batch.bgpos, c->batch.bsort, c->batch.bmu, c->batch.sig,
-                         c->batch.XB, c->batch.XBn, c->batch.VB};
-    for (const void* p : all)
-        if (!p) {
-            ital_ctx_destroy(c);
-            return ital_fail(-12, "ital_ctx_create: out of device memory");
-        }
+    ital_state st;
+    if (!st.alloc(*c, ALL)) {
+        ital_ctx_destroy(c);
+        return ital_fail(-12, "ital_ctx_create: out of device memory");
+    }
+    c->commit(*c, std::move(st));
     c->seen.assign((size_t)n_total, 0);
     ital_mvn_seed(c->mvn_state);
     *out = c;
@@ -116,9 +110,7 @@ extern "C" int ital_ctx_create(int64_t n_total, int d, double length_scale, doub
 // when on_device != 0.  Resets the labelled set (reference retrieval_base.py:34-61).
 extern "C" int ital_ctx_fit(ital_ctx* c, const double* rows, int on_device, hipStream_t stream) {
     if (!c || (!rows && c->n > 0)) return ital_fail(-22, "ital_ctx_fit: bad arguments");
-    if (c->n > 0 &&
-        hipMemcpy2DAsync(c->X, (size_t)c->ldx * sizeof(double), rows, (size_t)c->d * sizeof(double), (size_t)c->d * sizeof(double),
-                         (size_t)c->n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream) != hipSuccess)
+    if (c->n > 0 && !copy_rows(c->X, c->ldx, rows, c->d, c->n, on_device != 0, stream))
         return ital_fail(-5, "ital_ctx_fit: copy of the rows failed");
     if (c->n > 0) {
         const int rc = ital_row_norms(c->X, c->n, c->ldx, c->xn, stream);
@@ -126,9 +118,8 @@ extern "C" int ital_ctx_fit(ital_ctx* c, const double* rows, int on_device, hipS
     }
     // prior: mean 0, variance var; no labelled sample
     if (hipMemsetAsync(c->mu, 0, (size_t)c->ldv * sizeof(double), stream) != hipSuccess) return ital_fail(-5, "ital_ctx_fit: memset failed");
-    std::vector<double> v((size_t)c->ldv, c->var);
-    if (hipMemcpyAsync(c->s2, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
+    std::vector<double> v;
+    if (!fill_var(c->s2, 0, c->ldv, c->var, v, stream) || hipStreamSynchronize(stream) != hipSuccess)
         return ital_fail(-5, "ital_ctx_fit: upload failed");
     (void)hipMemsetAsync(c->status, 0, sizeof(int), stream);
     c->m = 0;
@@ -167,7 +158,7 @@ extern "C" int ital_ctx_update(ital_ctx* c, const int64_t* idx, const double* y,
     const bool via_comm = !all_batch && c->comm != nullptr;
     if (!all_batch && !all_local && !via_comm)
         return ital_fail(-38, "ital_ctx_update: rows of other ranks need the communicator (ital_ctx_create: nccl_comm)");
-    const int rec_len = ital_record_len(c->ldx, c->cap, c->kmax);
+    const int rec_len = record_len(c);
     for (int j0 = 0; j0 < c_new; j0 += 16) {
         const int cc = std::min(16, c_new - j0);
         ital_label_batch lb;
@@ -178,10 +169,7 @@ extern "C" int ital_ctx_update(ital_ctx* c, const int64_t* idx, const double* y,
             lb.y[j] = y[j0 + j];
         }
         if (via_comm) {
-            if (!c->stage) {
-                c->stage = dalloc<double>(c, (size_t)16 * c->ldx);
-                if (!c->stage) return ital_fail(-12, "ital_ctx_update: out of device memory");
-            }
+            if (c->stage.ensure((int64_t)16 * c->ldx) < 0) return ital_fail(-12, "ital_ctx_update: out of device memory");
             for (int j = 0; j < cc; j++) {
                 const int64_t gi = idx[j0 + j];
                 const int owner = owner_of(c, gi);
@@ -230,15 +218,9 @@ extern "C" int ital_ctx_revoke(ital_ctx* c, const int64_t* idx, int c_rev, hipSt
     }
     std::sort(pos.begin(), pos.end(), [](int a, int b) { return a > b; });
     if (std::adjacent_find(pos.begin(), pos.end()) != pos.end()) return ital_fail(-22, "ital_ctx_revoke: a sample named twice");
-    if (!c->rwork) {
-        c->rwork = dalloc<double>(c, (size_t)ital_gp_remove_workspace(c->cap));
-        if (!c->rwork) return ital_fail(-12, "ital_ctx_revoke: out of device memory");
-    }
+    if (c->rwork.ensure(ital_gp_remove_workspace(c->cap)) < 0) return ital_fail(-12, "ital_ctx_revoke: out of device memory");
     for (int p : pos) {
-        ital_remove_desc r = {};
-        r.XT = c->XT; r.XTn = c->XTn; r.ldx = c->ldx; r.L = c->L; r.ldl = c->cap; r.alpha = c->alpha;
-        r.V = c->V; r.ldv = c->ldv; r.n = c->n; r.mu = c->mu; r.s2 = c->s2; r.m = c->m; r.p = p;
-        r.work = c->rwork; r.work_doubles = ital_gp_remove_workspace(c->cap); r.status = c->status;
+        const ital_remove_desc r = remove_desc(*c, *c, c->m, p, c->rwork, c->status);
         const int rc = ital_gp_remove(&r, stream);
         if (rc) return rc;
         c->seen[(size_t)c->order[(size_t)p]] = 0;
@@ -267,29 +249,11 @@ int load_list(ital_ctx* c, const std::vector<int64_t>& list, int64_t* nc_out, in
         }
     const int64_t nc = (int64_t)rows.size();
     const bool contiguous = nc == 0 || pos.back() - pos.front() == nc - 1;
-    if (nc > c->cand_cap) {
-        // (sized for all of this rank's rows at once: grows at most once per context)
-        int rc = release(c, stream, {c->cand, c->alive, c->mi});
-        if (rc) return rc;
-        c->cand_cap = std::max<int64_t>(nc, c->n);
-        c->cand = dalloc<int32_t>(c, c->cand_cap);
-        c->alive = dalloc<uint8_t>(c, c->cand_cap);
-        c->mi = dalloc<double>(c, c->cand_cap);
-        if (!c->cand || !c->alive || !c->mi) {
-            c->cand_cap = 0;
-            return ital_fail(-12, "ital_ctx_fetch: out of device memory");
-        }
-    }
-    if (!contiguous && nc > c->gpos_cap) {
-        int rc = release(c, stream, {c->gpos});
-        if (rc) return rc;
-        c->gpos_cap = std::max<int64_t>(nc, c->n);
-        c->gpos = dalloc<int64_t>(c, c->gpos_cap);
-        if (!c->gpos) {
-            c->gpos_cap = 0;
-            return ital_fail(-12, "ital_ctx_fetch: out of device memory");
-        }
-    }
+    // (sized for all of this rank's rows at once: grows at most once per context)
+    const int64_t room = nc > 0 ? std::max<int64_t>(nc, c->n) : 0;
+    int rc = grow(stream, "ital_ctx_fetch: out of device memory", want(c->cand, room), want(c->alive, room), want(c->mi, room));
+    if (rc >= 0 && !contiguous) rc = grow(stream, "ital_ctx_fetch: out of device memory", want(c->gpos, room));
+    if (rc < 0) return rc;
     if (nc > 0 && (hipMemcpyAsync(c->cand, rows.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
                    hipMemsetAsync(c->alive, 1, nc, stream) != hipSuccess ||
                    (!contiguous && hipMemcpyAsync(c->gpos, pos.data(), nc * sizeof(int64_t), hipMemcpyHostToDevice, stream) != hipSuccess)))
@@ -297,7 +261,7 @@ int load_list(ital_ctx* c, const std::vector<int64_t>& list, int64_t* nc_out, in
     if (hipStreamSynchronize(stream) != hipSuccess) return ital_fail(-5, "ital_ctx_fetch: stream error");   // (rows, pos leave scope)
     *nc_out = nc;
     *pos_offset = nc > 0 ? pos.front() : 0;
-    *gpos_out = contiguous ? nullptr : c->gpos;
+    *gpos_out = contiguous ? nullptr : c->gpos.p;
     return 0;
 }
 
@@ -306,44 +270,25 @@ int load_list(ital_ctx* c, const std::vector<int64_t>& list, int64_t* nc_out, in
 // plus the picks up to ITAL_GENERIC_MAX_DIM rows of C).  The rows of the last batch go with the old batch state.
 int ensure_kmax(ital_ctx* c, int kmax, hipStream_t stream) {
     if (kmax <= c->kmax) return 0;
-    ital_batch& b = c->batch;
-    int rc = release(c, stream, {c->C, c->ret, c->rec, c->rec_all, b.bidx, b.bgpos, b.bsort, b.bmu, b.sig, b.XB, b.XBn, b.VB});
-    if (rc) return rc;
+    ital_dims nd = *c;
+    nd.kmax = kmax;
+    ital_state nw;
+    if (!drain(stream)) return ital_fail(-5, "ital_ctx: stream error");
+    if (!nw.alloc(nd, BY_KMAX)) return ital_fail(-12, "ital_ctx_fetch: out of device memory (batch state)");
     c->last_picks.clear();
-    c->kmax = kmax;
-    const int rec_len = ital_record_len(c->ldx, c->cap, kmax);
-    c->C = dalloc<double>(c, (size_t)kmax * c->ldv);
-    c->ret = dalloc<int64_t>(c, kmax + 1);
-    c->rec = dalloc<double>(c, rec_len);
-    c->rec_all = dalloc<double>(c, (size_t)c->world * rec_len);
-    b.kmax = kmax;
-    b.bidx = dalloc<int64_t>(c, kmax);
-    b.bgpos = dalloc<int64_t>(c, kmax);
-    b.bsort = dalloc<int32_t>(c, kmax);
-    b.bmu = dalloc<double>(c, kmax);
-    b.sig = dalloc<double>(c, (size_t)kmax * kmax);
-    b.XB = dalloc<double>(c, (size_t)kmax * c->ldx);
-    b.XBn = dalloc<double>(c, kmax);
-    b.VB = dalloc<double>(c, (size_t)kmax * c->cap);
-    const void* all[] = {c->C, c->ret, c->rec, c->rec_all, b.bidx, b.bgpos, b.bsort, b.bmu, b.sig, b.XB, b.XBn, b.VB};
-    for (const void* p : all)
-        if (!p) return ital_fail(-12, "ital_ctx_fetch: out of device memory (batch state)");
+    c->commit(nd, std::move(nw));
     return 0;
 }
 
-// The lattice scorer's workspace (ital_round_workspace) or the general scorer's pipeline workspace: grown to `want` doubles.
-int ensure_qwork(ital_ctx* c, int64_t want, hipStream_t stream) {
-    if (want <= c->qwork_doubles) return 0;
-    int rc = release(c, stream, {c->qwork});
-    if (rc) return rc;
-    c->qwork = dalloc<double>(c, (size_t)want);
-    c->qwork_doubles = c->qwork ? want : 0;
-    return c->qwork ? 0 : ital_fail(-12, "ital_ctx_fetch: out of device memory (workspace)");
+// The lattice scorer's workspace (ital_round_workspace) or the general scorer's pipeline workspace: grown to `doubles`.
+int ensure_qwork(ital_ctx* c, int64_t doubles, hipStream_t stream) {
+    const int rc = grow(stream, "ital_ctx_fetch: out of device memory (workspace)", want(c->qwork, doubles));
+    return rc < 0 ? rc : 0;
 }
 
 // Selection of greedy step t (member slot t - 1) out of the scores c->mi: arg-max, record, append to the batch state.
 int select_step(ital_ctx* c, int t, int64_t nc, int64_t pos_offset, const int64_t* gpos, hipStream_t stream) {
-    const int rec_len = ital_record_len(c->ldx, c->cap, c->kmax);
+    const int rec_len = record_len(c);
     if (c->world == 1 && !c->comm)
         return ital_select_fused(c->mi, c->cand, c->alive, nc, pos_offset, gpos, c->row0, c->rank, 0, c->mu, c->s2, c->X, c->xn,
                                  c->ldx, c->V, c->ldv, c->m, c->cap, c->C, c->ldv, t - 1, t - 1, c->batch, c->status, c->rec, c->ret,
@@ -377,9 +322,8 @@ int download_ret(ital_ctx* c, std::vector<int64_t>& host, hipStream_t stream) {
 int lattice_round(ital_ctx* c, int k, int64_t nc, int64_t pos_offset, const int64_t* gpos, int64_t n_list, int label_mode,
                   std::vector<int64_t>& host, hipStream_t stream) {
     // the lattice scorer's workspace, ONCE for the whole round: what its largest step (t = k) needs, capped at 1 GiB (slabs
-    // beyond) -- ital_round_workspace is documented for exactly this.  (Until round 6 it was sized per step: each of the steps
-    // t = 3 .. k allocated a larger buffer and left the previous one in `owned` until ital_ctx_destroy, up to ~5 GiB stranded
-    // after the first k = 8 fetch at large n.)
+    // beyond) -- ital_round_workspace is documented for exactly this (sized per step, each of the steps t = 3 .. k would grow it
+    // again).
     if (k >= 3) {
         const int rc = ensure_qwork(c, ital_round_workspace(k, std::max<int64_t>(nc, 1), kQworkCap), stream);
         if (rc) return rc;
@@ -399,17 +343,13 @@ int lattice_round(ital_ctx* c, int k, int64_t nc, int64_t pos_offset, const int6
                 std::vector<double> vk(t - 1);
                 int rc = ital_mvn_tables(t, jump.data(), pat.data(), vk.data());
                 if (rc) return rc;
-                c->jump[t] = dalloc<long long>(c, jump.size());
-                c->jumppat[t] = dalloc<long long>(c, pat.size());
-                c->vk[t] = dalloc<double>(c, vk.size());
-                if (!c->jump[t] || !c->jumppat[t] || !c->vk[t]) return ital_fail(-12, "ital_ctx_fetch: out of device memory");
-                if (hipMemcpy(c->jump[t], jump.data(), jump.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(c->jumppat[t], pat.data(), pat.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(c->vk[t], vk.data(), vk.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-                    return ital_fail(-5, "ital_ctx_fetch: upload of the stream tables failed");
+                DevBuf<long long> d_jump, d_pat;
+                DevBuf<double> d_vk;
+                if ((rc = upload_table(d_jump, jump)) || (rc = upload_table(d_pat, pat)) || (rc = upload_table(d_vk, vk))) return rc;
+                c->jump[t] = std::move(d_jump); c->jumppat[t] = std::move(d_pat); c->vk[t] = std::move(d_vk);
             }
             desc.jump = c->jump[t]; desc.jumppat = c->jumppat[t]; desc.vk = c->vk[t];
-            desc.work = c->qwork; desc.work_doubles = c->qwork_doubles;
+            desc.work = c->qwork; desc.work_doubles = c->qwork.count;
             for (int j = 0; j < 6; j++) desc.seed[j] = c->mvn_state[j];
         }
         int rc = nc > 0 ? ital_score_step(&desc, stream) : 0;
@@ -447,16 +387,10 @@ int generic_tables(ital_ctx* c) {
     for (int i = 0; i < 64; i++) iota[(size_t)i] = i;
     int rc = ital_mvn_generic_tables(GN, jump1.data(), vk.data());
     if (rc) return rc;
-    long long* j1 = dalloc<long long>(c, jump1.size());
-    c->vk_all = dalloc<double>(c, vk.size());
-    c->iota = dalloc<int32_t>(c, iota.size());
-    c->zero64 = dalloc<int64_t>(c, 1);
-    if (!j1 || !c->vk_all || !c->iota || !c->zero64) return ital_fail(-12, "ital_ctx_fetch: out of device memory");
-    if (hipMemcpy(j1, jump1.data(), jump1.size() * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->vk_all, vk.data(), vk.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->iota, iota.data(), iota.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return ital_fail(-5, "ital_ctx_fetch: upload of the stream tables failed");
-    c->jump1 = j1;
+    DevBuf<long long> d_jump1;                                  // (c->jump1 says that all four are there)
+    if ((rc = upload_table(d_jump1, jump1)) || (rc = upload_table(c->vk_all, vk)) || (rc = upload_table(c->iota, iota))) return rc;
+    if (!c->zero64.alloc(1)) return ital_fail(-12, "ital_ctx_fetch: out of device memory");
+    c->jump1 = std::move(d_jump1);
     return 0;
 }
 
@@ -476,7 +410,7 @@ int gscore_workspace(ital_ctx* c, ital_gscore_desc& d, hipStream_t stream) {
     const int64_t want = std::min<int64_t>(ital_score_generic_workspace(&d), kQworkCap);
     const int rc = ensure_qwork(c, want, stream);
     if (rc) return rc;
-    d.work = c->qwork; d.work_doubles = c->qwork_doubles;
+    d.work = c->qwork; d.work_doubles = c->qwork.count;
     return 0;
 }
 
@@ -518,7 +452,7 @@ int generic_round(ital_ctx* c, int k, int64_t nc, int64_t pos_offset, const int6
 // whitened column behind it, and (n_cc > 0) C[0 .. n_cc)[gi] behind that -- and replicated: the address of the owner's record
 // on this rank (c->rec itself without a communicator).
 int share_sample(ital_ctx* c, int64_t gi, int n_cc, const double** out, hipStream_t stream) {
-    const int h = ITAL_REC_HEADER, rec_len = ital_record_len(c->ldx, c->cap, c->kmax);
+    const int h = ITAL_REC_HEADER, rec_len = record_len(c);
     const int owner = owner_of(c, gi);
     if (hipMemsetAsync(c->rec, 0, (size_t)rec_len * sizeof(double), stream) != hipSuccess) return ital_fail(-5, "ital_ctx_fetch: memset failed");
     if (owner == c->rank) {
@@ -571,7 +505,7 @@ int subset_round(ital_ctx* c, int k, const std::vector<int64_t>& list, std::vect
                  const int64_t* gpos, std::vector<int64_t>& picks, hipStream_t stream) {
     int rc = generic_tables(c);
     if (rc) return rc;
-    const int h = ITAL_REC_HEADER, rec_len = ital_record_len(c->ldx, c->cap, c->kmax);
+    const int h = ITAL_REC_HEADER, rec_len = record_len(c);
     const int fb_mode = fb_mode_of(c->model);
     const int kmax_e = (int)E.size() + k;
     std::unordered_map<int64_t, int64_t> pos_of;
@@ -579,13 +513,8 @@ int subset_round(ital_ctx* c, int k, const std::vector<int64_t>& list, std::vect
     // staging of the base set on the device: E_idx, in_pos, dead_pos [kmax_e] int64, E_mu [kmax_e], E_sig [kmax_e]^2,
     // E_sort, pick_pos [kmax_e] int32
     const int64_t bytes = (int64_t)8 * (4 * kmax_e + (int64_t)kmax_e * kmax_e) + 8 * kmax_e + 64;
-    if (bytes > c->sub_bytes) {
-        if ((rc = release(c, stream, {c->sub}))) return rc;
-        c->sub = dalloc<char>(c, (size_t)bytes);
-        c->sub_bytes = c->sub ? bytes : 0;
-        if (!c->sub) return ital_fail(-12, "ital_ctx_fetch: out of device memory");
-    }
-    int64_t* d_eidx = reinterpret_cast<int64_t*>(c->sub);
+    if ((rc = grow(stream, "ital_ctx_fetch: out of device memory", want(c->sub, bytes))) < 0) return rc;
+    int64_t* d_eidx = reinterpret_cast<int64_t*>(c->sub.p);
     int64_t* d_in = d_eidx + kmax_e;
     int64_t* d_dead = d_in + kmax_e;
     double* d_emu = reinterpret_cast<double*>(d_dead + kmax_e);
@@ -786,9 +715,7 @@ int model_fetch(ital_ctx* c, const char* who, int k, const int64_t* cand, int64_
         if (rc) return rc;
         list.assign(cand, cand + n_cand);
     } else {
-        list.reserve((size_t)n_unseen);
-        for (int64_t i = 0; i < c->n_total; i++)
-            if (!c->seen[(size_t)i]) list.push_back(i);
+        list = unlabelled(c);
     }
     std::vector<int64_t> E;
     bool whole_list = false;
@@ -824,7 +751,7 @@ int model_fetch(ital_ctx* c, const char* who, int k, const int64_t* cand, int64_
         if (n_subset > 0) {
             if ((rc = subset_round(c, steps, list, E, nc, pos_offset, gpos, got, stream))) return rc;
             int s = 0;
-            if (hipMemcpy(&s, c->status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ital_fail(-5, "ital_ctx_fetch: stream error");
+            if ((rc = read_status(c, &s))) return rc;
             st = s;
         } else {
             bool generic = !perfect_user(c->model);
@@ -837,9 +764,7 @@ int model_fetch(ital_ctx* c, const char* who, int k, const int64_t* cand, int64_
                     // the labels (large noise): the round again through the general scorer from the same stream position
                     // (ital.py:411-417)
                     int s = 0;
-                    if (hipMemcpy(&s, c->status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ital_fail(-5, "ital_ctx_fetch: stream error");
-                    s &= ~6;
-                    if (hipMemcpy(c->status, &s, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return ital_fail(-5, "ital_ctx_fetch: stream error");
+                    if ((rc = read_status(c, &s)) || (rc = write_status(c, s & ~6))) return rc;
                     memcpy(c->mvn_state, saved, sizeof(saved));
                     if ((rc = load_list(c, list, &nc, &pos_offset, &gpos, stream))) return rc;
                     generic = true;
@@ -877,10 +802,7 @@ extern "C" int ital_ctx_fetch(ital_ctx* c, int k, int64_t* picks, hipStream_t st
     if (k < 1) return 0;
     if (k > ITAL_MAX_T) return ital_fail(-22, "ital_ctx_fetch: batches larger than ITAL_MAX_T need the Monte-Carlo switch (ital_score_generic)");
     // candidate list: ascending unseen samples; this rank's share is one run of it
-    std::vector<int64_t> list;
-    list.reserve((size_t)n_unseen);
-    for (int64_t i = 0; i < c->n_total; i++)
-        if (!c->seen[(size_t)i]) list.push_back(i);
+    const std::vector<int64_t> list = unlabelled(c);
     int64_t nc = 0, pos_offset = 0;
     const int64_t* gpos = nullptr;
     std::vector<int64_t> host;
@@ -890,8 +812,7 @@ extern "C" int ital_ctx_fetch(ital_ctx* c, int k, int64_t* picks, hipStream_t st
     const int64_t st = host[(size_t)c->kmax];
     if (st & 1) return ital_fail(-33, "ital_ctx_fetch: kernel matrix of the labelled samples is not positive definite");
     if (st & 6) {
-        int zero = 0;
-        (void)hipMemcpy(c->status, &zero, sizeof(int), hipMemcpyHostToDevice);
+        (void)write_status(c, 0);
         return ital_fail(-71, "ital_ctx_fetch: the round needs the general scorer (duplicate samples in the batch or large noise)");
     }
     c->last_picks.assign(host.begin(), host.begin() + k);
@@ -936,8 +857,7 @@ extern "C" int ital_ctx_mcmi_fetch(ital_ctx* c, int k, const int64_t* cand, int6
         if (rc) return rc;
         list.assign(cand, cand + n_cand);
     } else {
-        for (int64_t i = 0; i < c->n_total; i++)
-            if (!c->seen[(size_t)i]) list.push_back(i);
+        list = unlabelled(c);
     }
     const int64_t nc = (int64_t)list.size();
     if (nc < k) k = (int)nc;
@@ -945,46 +865,23 @@ extern "C" int ital_ctx_mcmi_fetch(ital_ctx* c, int k, const int64_t* cand, int6
     if (k > ITAL_MAX_T) return ital_fail(-95, "ital_ctx_mcmi_fetch: batches larger than 8 are not enumerated on the device");
     c->last_picks.clear();
     const int ldc = pad16(nc), ldx = c->ldx, cap = c->cap;
-    int rc = 0;
-    if (nc > c->block_cap) {
-        if ((rc = release(c, stream, {c->Xc, c->vec, c->ce, c->cand64, c->bpos, c->balive}))) return rc;
-        c->block_cap = nc;
-        c->Xc = dalloc<double>(c, (size_t)nc * ldx);
-        c->vec = dalloc<double>(c, (size_t)3 * nc);
-        c->ce = dalloc<double>(c, nc);
-        c->cand64 = dalloc<int64_t>(c, nc);
-        c->bpos = dalloc<int32_t>(c, nc);
-        c->balive = dalloc<uint8_t>(c, nc);
-        if (!c->Xc || !c->vec || !c->ce || !c->cand64 || !c->bpos || !c->balive) {
-            c->block_cap = 0;
-            return ital_fail(-12, "ital_ctx_mcmi_fetch: out of device memory");
-        }
+    const char* oom = "ital_ctx_mcmi_fetch: out of device memory";
+    int rc = grow(stream, oom, want(c->Xc, nc * ldx), want(c->vec, 3 * nc), want(c->ce, nc), want(c->cand64, nc), want(c->bpos, nc),
+                  want(c->balive, nc));
+    if (rc < 0) return rc;
+    if (rc > 0) {
+        // (a grown bpos is zero again: block positions 0, 1, 2, ...)
         std::vector<int32_t> pos((size_t)nc);
         for (int64_t i = 0; i < nc; i++) pos[(size_t)i] = (int32_t)i;
         if (hipMemcpy(c->bpos, pos.data(), pos.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
             return ital_fail(-5, "ital_ctx_mcmi_fetch: upload failed");
     }
-    if ((int64_t)ldc * nc > c->cov_cap) {
-        // Vc [cap][ldc] and the covariance block [nc][ldc] follow the block's padded width
-        if ((rc = release(c, stream, {c->Vc, c->cov}))) return rc;
-        c->cov_cap = (int64_t)ldc * nc;
-        c->Vc = dalloc<double>(c, (size_t)cap * ldc);
-        c->cov = dalloc<double>(c, (size_t)c->cov_cap);
-        if (!c->Vc || !c->cov) {
-            c->cov_cap = 0;
-            return ital_fail(-12, "ital_ctx_mcmi_fetch: out of device memory");
-        }
-    }
+    // Vc [cap][ldc] and the covariance block [nc][ldc] follow the block's padded width
+    if ((rc = grow(stream, oom, want(c->Vc, (int64_t)cap * ldc), want(c->cov, (int64_t)ldc * nc))) < 0) return rc;
     const bool round = nc <= ((int64_t)1 << 18);
-    if (k >= 5) {
-        const int64_t want = ital_mcmi_workspace(ITAL_MAX_T, nc);
-        if (want > c->mwork_doubles) {
-            if ((rc = release(c, stream, {c->mwork}))) return rc;
-            c->mwork = dalloc<double>(c, (size_t)want);
-            c->mwork_doubles = c->mwork ? want : 0;
-            if (!c->mwork) return ital_fail(-12, "ital_ctx_mcmi_fetch: out of device memory (workspace)");
-        }
-    }
+    if (k >= 5 && (rc = grow(stream, "ital_ctx_mcmi_fetch: out of device memory (workspace)",
+                             want(c->mwork, ital_mcmi_workspace(ITAL_MAX_T, nc)))) < 0)
+        return rc;
     double *xnc = c->vec, *muc = c->vec + nc, *s2c = c->vec + 2 * nc;
     // (the padding columns of Vc stay zero: cleared before every gather, the block width may have changed)
     if (hipMemcpyAsync(c->cand64, list.data(), nc * sizeof(int64_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
@@ -998,7 +895,7 @@ extern "C" int ital_ctx_mcmi_fetch(ital_ctx* c, int k, const int64_t* cand, int6
     step.n_i = nc; step.pos_offset = 0; step.n_all = nc; step.alive = c->balive; step.mu = muc; step.s2 = s2c;
     step.cov = c->cov; step.ld_cov = ldc; step.C = c->C; step.ldc = ldc; step.batch = c->batch; step.noise = c->noise;
     step.eps = 1e-12; step.ce = c->ce;
-    if (k >= 5) { step.work = c->mwork; step.work_doubles = c->mwork_doubles; }
+    if (k >= 5) { step.work = c->mwork; step.work_doubles = c->mwork.count; }
     if (round) {
         ital_mcmi_round_desc r;
         memset(&r, 0, sizeof(r));
@@ -1013,7 +910,7 @@ extern "C" int ital_ctx_mcmi_fetch(ital_ctx* c, int k, const int64_t* cand, int6
             return ital_fail(-5, "ital_ctx_mcmi_fetch: memset failed");
         rc = ital_cov_block(c->Xc, xnc, nc, c->Xc, xnc, nc, ldx, c->Vc, ldc, c->Vc, ldc, c->m, c->var, c->length_scale, c->cov, ldc,
                             stream);
-        const int rec_len = ital_record_len(ldx, cap, c->kmax);
+        const int rec_len = record_len(c);
         for (int t = 1; t <= k && !rc; t++) {
             step.t = t;
             rc = ital_mcmi_score_step(&step, stream);
@@ -1043,18 +940,10 @@ extern "C" int ital_ctx_top_results(ital_ctx* c, int k, int64_t* idx, hipStream_
     if (k < 1 || k > std::min<int64_t>(ITAL_TOPK_MAX, c->n_total))
         return ital_fail(-22, "ital_ctx_top_results: k outside 1..min(ITAL_TOPK_MAX, number of samples)");
     int rc = 0;
-    if (!c->tk_work) {
-        c->tk_work = dalloc<char>(c, (size_t)ital_topk_workspace());
-        if (!c->tk_work) return ital_fail(-12, "ital_ctx_top_results: out of device memory");
-    }
-    if (k > c->tk_cap) {
-        // per rank: [k values][k indices (int64 bits)], all ranks' behind each other
-        if ((rc = release(c, stream, {c->tk_send, c->tk_all}))) return rc;
-        c->tk_send = dalloc<double>(c, (size_t)2 * k);
-        c->tk_all = dalloc<double>(c, (size_t)2 * k * c->world);
-        c->tk_cap = (c->tk_send && c->tk_all) ? k : 0;
-        if (!c->tk_cap) return ital_fail(-12, "ital_ctx_top_results: out of device memory");
-    }
+    const char* oom = "ital_ctx_top_results: out of device memory";
+    if (c->tk_work.ensure((int64_t)ital_topk_workspace()) < 0) return ital_fail(-12, oom);
+    // per rank: [k values][k indices (int64 bits)], all ranks' behind each other
+    if ((rc = grow(stream, oom, want(c->tk_send, 2 * k), want(c->tk_all, 2 * k * c->world))) < 0) return rc;
     const int k_loc = (int)std::min<int64_t>(k, c->n);
     if (k_loc > 0 && (rc = ital_topk(c->mu, c->n, c->row0, k_loc, c->tk_send, reinterpret_cast<int64_t*>(c->tk_send + k), c->tk_work,
                                      stream)))
@@ -1092,20 +981,14 @@ extern "C" int ital_ctx_top_results(ital_ctx* c, int k, int64_t* idx, hipStream_
 extern "C" int ital_ctx_predict(ital_ctx* c, const double* Xt, int64_t nt, double* mean, double* variance, hipStream_t stream) {
     if (!c || !c->fitted || nt < 0 || (nt > 0 && !Xt)) return ital_fail(-22, "ital_ctx_predict: bad arguments");
     if (c->m == 0) return ital_fail(-22, "ital_ctx_predict: needs a fitted relevance model: call ital_ctx_update first");
-    if (!c->pXt) {
-        // (the padding columns of pXt stay zero: the uploads write d of ldx columns)
-        c->pXt = dalloc<double>(c, (size_t)kPredictChunk * c->ldx);
-        c->pxtn = dalloc<double>(c, kPredictChunk);
-        c->pVt = dalloc<double>(c, (size_t)c->cap * kPredictChunk);
-        c->pmean = dalloc<double>(c, kPredictChunk);
-        c->pvar = dalloc<double>(c, kPredictChunk);
-        if (!c->pXt || !c->pxtn || !c->pVt || !c->pmean || !c->pvar) return ital_fail(-12, "ital_ctx_predict: out of device memory");
-    }
+    // (the padding columns of pXt stay zero: the uploads write d of ldx columns)
+    if (c->pXt.ensure(kPredictChunk * c->ldx) < 0 || c->pxtn.ensure(kPredictChunk) < 0 || c->pVt.ensure(c->cap * kPredictChunk) < 0 ||
+        c->pmean.ensure(kPredictChunk) < 0 || c->pvar.ensure(kPredictChunk) < 0)
+        return ital_fail(-12, "ital_ctx_predict: out of device memory");
     for (int64_t i0 = 0; i0 < nt; i0 += kPredictChunk) {
         const int64_t cnt = std::min<int64_t>(kPredictChunk, nt - i0);
         const int64_t ldvt = pad16(cnt);
-        if (hipMemcpy2DAsync(c->pXt, (size_t)c->ldx * sizeof(double), Xt + (size_t)i0 * c->d, (size_t)c->d * sizeof(double),
-                             (size_t)c->d * sizeof(double), (size_t)cnt, hipMemcpyHostToDevice, stream) != hipSuccess)
+        if (!copy_rows(c->pXt, c->ldx, Xt + (size_t)i0 * c->d, c->d, cnt, false, stream))
             return ital_fail(-5, "ital_ctx_predict: upload of the points failed");
         int rc = ital_predict(c->pXt, cnt, c->ldx, c->XT, c->XTn, c->m, c->L, c->cap, c->alpha, c->var, c->length_scale, c->pmean,
                               c->pvar, c->pxtn, c->pVt, ldvt, 1, stream);

@@ -93,9 +93,19 @@ class Ctx:
         rc = self.lib.ital_ctx_fetch(self.h, k, p.ctypes.data, None)
         return rc, p[: max(rc, 0)].tolist()
 
-    def mcmi_fetch(self, k):
+    def fetch_list(self, k, cand, subset=()):
+        """k picks out of the candidate list `cand`, optionally with a change-estimation subset."""
+        cand, subset = _i64(cand), _i64(subset)
         p = np.zeros(max(k, 1), dtype=np.int64)
-        rc = self.lib.ital_ctx_mcmi_fetch(self.h, k, None, 0, p.ctypes.data, None)
+        rc = self.lib.ital_ctx_fetch_list(self.h, k, cand.ctypes.data, len(cand), subset.ctypes.data if len(subset) else None,
+                                          len(subset), p.ctypes.data, None)
+        return rc, p[: max(rc, 0)].tolist()
+
+    def mcmi_fetch(self, k, cand=None):
+        p = np.zeros(max(k, 1), dtype=np.int64)
+        cand = None if cand is None else _i64(cand)
+        rc = self.lib.ital_ctx_mcmi_fetch(self.h, k, None if cand is None else cand.ctypes.data, 0 if cand is None else len(cand),
+                                          p.ctypes.data, None)
         return rc, p[: max(rc, 0)].tolist()
 
     def predict_stored(self):
@@ -439,6 +449,74 @@ def test_reserve_lifts_the_capacity(lib):
         assert_same_state(a, b)
         # 48 is a capacity like any other: 49 labels do not fit, 37 is rounded up to 48
         assert a.reserve(37) == 0 and a.try_update(list(range(141, 150)) + list(range(111, 118)) + list(range(82, 95))) == -12
+    finally:
+        a.close()
+        b.close()
+
+
+# ------------------------------------------------------------------ scratch that was in use when the shape changed
+# 40 unlabelled candidates below row 150 that no case removes, and a change-estimation subset of 7: five of them, two others
+_FREE = [i for i in range(1, 149) if i not in LABELLED and i != 88]
+CAND = _FREE[::3][:40]
+SUBSET = CAND[2::9][:5] + [i for i in _FREE if i not in CAND][5:7]
+GONE = [0, 88, 149, 160, 186]                             # unlabelled, outside CAND and SUBSET
+POINTS = XALL[187:192]                                    # rows of no context
+
+
+def _session(c, num):
+    """The calls that grow every lazily grown buffer of a context, `num` giving the context's number of every row of XALL:
+    the candidate buffers, the scorers' workspace and the stream tables (lattice scorer, k = 4), the batch state at kmax = 9
+    and the subset staging (general scorer), the MCMI block with its covariances and workspace (k = 5), the top-k and
+    predict scratch, the workspace of ital_gp_remove.  The last label is taken back and given again, which keeps the
+    insertion order.  Returns the index lists and the float64 arrays."""
+    cand, subset, last = num[CAND], num[SUBSET], int(num[LABELLED[-1]])
+    lists = [c.fetch_list(4, cand), c.fetch_list(2, cand, subset), c.mcmi_fetch(5, cand)]
+    assert [r[0] for r in lists] == [4, 2, 5], (c.err(), lists)
+    rc, top = c.top_results(10)
+    assert rc == 0, c.err()
+    rc, mean, var = c.predict(POINTS)
+    assert rc == 0, c.err()
+    assert c.revoke([last]) == 0, c.err()
+    c.update([last], YALL[LABELLED[-1:]])
+    return [r[1] for r in lists] + [top], [mean, var]
+
+
+@pytest.mark.parametrize("case", ["reserve", "add_rows", "remove_rows", "remove_rows_labelled"])
+def test_scratch_in_use_survives_a_change_of_shape(lib, case):
+    """Context a has used every lazily grown buffer when its capacity or its rows change, and uses them all again; context b
+    makes the same calls at the final shape from the start, so its scratch is never dropped.  Explicit candidate lists keep
+    both at the same position of mvndst's stream, which advances by the length of the list.  A labelled row's removal does
+    not equal a fresh factorisation in bits: there b takes the label back first (the equality stated above)."""
+    from ital_amd.device_data import removal_map
+    before_a = before_b = after = np.arange(len(XALL))    # the numbering of XALL's rows in a / b before the call, in both after
+    if case == "reserve":
+        a, b = Ctx(lib, X, capacity=32), Ctx(lib, X, capacity=64)
+    elif case == "add_rows":
+        a, b = Ctx(lib, X), Ctx(lib, XALL[:187])
+    elif case == "remove_rows":
+        after = before_b = removal_map(187, GONE)
+        a, b = Ctx(lib, XALL[:187]), Ctx(lib, np.delete(XALL[:187], GONE, 0))
+    else:
+        after = removal_map(N, REMOVED)
+        a, b = Ctx(lib, X), Ctx(lib, X)
+    try:
+        for c, num in ((a, before_a), (b, before_b)):
+            c.update(num[BLOCK_A], YALL[BLOCK_A])
+            c.update(num[BLOCK_B], YALL[BLOCK_B])
+            _session(c, num)
+        if case == "reserve":
+            assert a.reserve(64) == 0, a.err()
+        elif case == "add_rows":
+            assert a.add_rows(XALL[150:187]) == 0, a.err()
+        elif case == "remove_rows":
+            assert a.remove_rows(GONE) == 0, a.err()
+        else:
+            assert a.remove_rows(REMOVED) == 0, a.err()
+            assert b.revoke([7]) == 0 and b.remove_rows(REMOVED) == 0, b.err()
+        (lists_a, arrays_a), (lists_b, arrays_b) = _session(a, after), _session(b, after)
+        assert lists_a == lists_b
+        for va, vb in zip(arrays_a, arrays_b):
+            assert np.array_equal(va, vb), np.abs(va - vb).max()
     finally:
         a.close()
         b.close()
