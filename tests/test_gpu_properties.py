@@ -100,6 +100,42 @@ def test_selection_inside_the_scoring_launch_equals_the_separate_launch(dev, n, 
             np.testing.assert_array_equal(x, y)
 
 
+@pytest.mark.parametrize("n", [33, 300])
+@pytest.mark.parametrize("round_call", [False, True])
+def test_selection_inside_the_scoring_launch_equals_the_host_model(dev, n, round_call):
+    """The companion of the test above: what select_tail picks, step by step, is what the exact host model of the rule
+    (tests/_select_ref.py) picks from the scores that step left, over the positions still alive."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _select_ref as ref
+    from ital_amd import ITAL, mvn_stream
+    k = 4
+    rng = np.random.default_rng(4)
+    X = rng.random((n, 10))
+    X[n // 2] = X[n // 3]                      # an exact twin, as in the test above
+    mvn_stream.GLOBAL.reset()
+    L = ITAL(X, length_scale=0.9, device=dev)
+    L.round_call = round_call
+    L.select_in_scorer = True
+    L.keep_scores = True
+    L.update({0: 1, 1: -1})
+    unseen = np.asarray(L._unseen_array())
+    ret = L.fetch_unlabelled(k)
+    b = L._fetch_bufs
+    bidx, bgpos, bsort, dev_ret = (b[q].cpu().numpy() for q in ("bidx", "bgpos", "bsort", "ret"))
+    assert len(L.last_scores) == k and list(dev_ret[:k]) == ret
+    for t, s_ in enumerate(L.last_scores):
+        s_ = s_.cpu().numpy()[: len(unseen)]
+        alive = np.ones(len(unseen), dtype=np.uint8)
+        alive[np.searchsorted(unseen, ret[:t])] = 0          # the positions picked before step t
+        val, lp, loc = ref.pick(s_, alive, 0, 0)
+        assert lp == loc and (ret[t], bidx[t], bgpos[t]) == (unseen[lp], unseen[lp], lp), t
+    assert list(bsort[:k]) == list(np.argsort(bidx[:k], kind="stable"))
+    alive[np.searchsorted(unseen, ret[k - 1:])] = 0
+    assert np.array_equal(b["alive"][: len(unseen)].cpu().numpy(), alive)
+
+
 def test_device_candidate_list_follows_arbitrary_feedback(dev):
     """The candidate list kept on the device between rounds is reused only when the host's list is the previous one minus
     exactly the previous batch; partial feedback, feedback for other samples, unnameable feedback and reset() must fall back
