@@ -8,7 +8,7 @@ The arithmetic lives in hand-written HIP kernels (ital_amd/csrc, C ABI in includ
 from . import mvn_stream
 from .mvn_stream import GLOBAL as mvn_global_stream
 
-__all__ = ["ITAL", "MCMI_min", "AdaptAL", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode"]
+__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode"]
 
 
 def serving_mode():
@@ -38,6 +38,9 @@ def __getattr__(name):
     if name == "AdaptAL":
         from .adapt_al import AdaptAL
         return AdaptAL
+    if name in ("TCAL", "RBMAL"):
+        from . import competitors
+        return getattr(competitors, name)
     if name == "DeviceData":
         from .device_data import DeviceData
         return DeviceData

@@ -1,6 +1,6 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
 include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_evidence_grad.h,
-include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h and include/ital_compact.h).
+include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h and include/ital_cosine.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -327,6 +327,12 @@ CTX_LIVE_SIGNATURES = {
 }
 
 
+#: the kernel of the RBMAL learner (cosine distance to the nearest labelled row), declared in include/ital_cosine.h
+COSINE_SIGNATURES = {
+    "ital_cosine_min": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -349,7 +355,7 @@ def load(path=LIB_PATH):
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
-            list(CTX_LIVE_SIGNATURES.items()):
+            list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -3,8 +3,9 @@ acquisition score is a function of what the streaming GP already keeps on the GP
 TopscoringSampling, BorderlineSampling, BorderlineDiversitySampling, VarianceSampling (with and without
 `use_correlations`), UncertaintySampling, EntropySampling (the orthant kernel of the ITAL scorer) and EMOC (the FP64
 MFMA covariance tiles of MCMI) -- reference ital/baseline_methods.py:12-155, :203-287, :338-381.  They exist so that the
-reference's comparison tables run through `ital_amd.harness` against the same GP; the remaining baselines (SUD, RBMAL,
-TCAL, USDM) use models of their own and are out of scope; AdaptAL is a learner of its own (ital_amd/adapt_al.py).
+reference's comparison tables run through `ital_amd.harness` against the same GP; AdaptAL is a learner of its own
+(ital_amd/adapt_al.py), so are TCAL and RBMAL (ital_amd/competitors.py); SUD and USDM, which need an N x N neighbour
+structure over the whole data set, are out of scope.
 """
 import numpy as np
 import torch

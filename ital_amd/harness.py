@@ -58,11 +58,15 @@ def read_config_file(config_file, section, overrides):
 def _learners():
     from . import ITAL, AdaptAL, MCMI_min
     from .baselines import LEARNERS as ranking
+    from .competitors import LEARNERS as competitors
     table = {"ITAL": ITAL, "MCMI": MCMI_min, "AdaptAL": AdaptAL}
     table.update(ranking)
+    table.update(competitors)
     return table
 
 
+#: the reference's comparison baselines with models of their own; TCAL and RBMAL have since become learners here
+#: (ital_amd/competitors.py: _learners() is looked up first), SUD and USDM are what is left
 BASELINES = ("SUD", "RBMAL", "TCAL", "USDM")
 
 
@@ -71,8 +75,9 @@ def make_learner(method, data, learner_config, **placement):
     if method not in table:
         if method in BASELINES:
             raise NotImplementedError("learner %r is one of the reference's comparison baselines that are not part of the "
-                                      "MI355X path (ITAL, MCMI, AdaptAL and the GP-sharing baselines random / topscoring / border / "
-                                      "border_div / var / unc / entropy / EMOC are)" % method)
+                                      "MI355X path: SUD and USDM, which need an N x N neighbour structure over the whole data set, "
+                                      "are what is left (ITAL, MCMI, AdaptAL, TCAL, RBMAL and the GP-sharing baselines random / "
+                                      "topscoring / border / border_div / var / unc / entropy / EMOC are covered)" % method)
         raise KeyError("unknown learner %r" % method)
     return table[method](data, **learner_config, **placement)
 
