@@ -216,6 +216,28 @@ REVOKE_SIGNATURES = {
 }
 
 
+class ItalInfluenceDesc(ctypes.Structure):
+    """ital_influence_desc (include/ital_influence.h): the GP state that is read, the row mask and where the tables go."""
+    _fields_ = [("L", c_void_p), ("ldl", c_int), ("alpha", c_void_p), ("m", c_int), ("V", c_void_p), ("ldv", c_int64),
+                ("n", c_int64), ("mu", c_void_p), ("s2", c_void_p), ("mask", c_void_p), ("coef", c_void_p), ("stats", c_void_p),
+                ("work", c_void_p), ("work_doubles", c_int64), ("status", c_void_p)]
+
+
+#: what taking each label back would change, declared in include/ital_influence.h
+INFLUENCE_SIGNATURES = {
+    "ital_gp_influence": (c_int, [ctypes.POINTER(ItalInfluenceDesc), c_void_p]),
+    "ital_gp_influence_workspace": (c_int64, [c_int, c_int64]),
+    "ital_gp_preview_remove": (c_int, [ctypes.POINTER(ItalInfluenceDesc), ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
+                                       c_int64, c_void_p]),
+}
+
+
+#: the audit of a context's labels, declared in include/ital_ctx_audit.h
+CTX_AUDIT_SIGNATURES = {
+    "ital_ctx_audit": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
+
 class ItalRewhitenDesc(ctypes.Structure):
     """ital_rewhiten_desc (include/ital_rewhiten.h): a range of data rows and the labelled-set state it is whitened against."""
     _fields_ = [("X", c_void_p), ("n_rows", c_int64), ("ldx", c_int), ("XT", c_void_p), ("XTn", c_void_p), ("L", c_void_p),
@@ -355,7 +377,8 @@ def load(path=LIB_PATH):
             list(ADAPT_SIGNATURES.items()) + list(REVOKE_SIGNATURES.items()) + list(REWHITEN_SIGNATURES.items()) + \
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
-            list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()):
+            list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()) + list(INFLUENCE_SIGNATURES.items()) + \
+            list(CTX_AUDIT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

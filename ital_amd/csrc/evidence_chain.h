@@ -1,7 +1,7 @@
 // What ital_gp_evidence (evidence.hip), ital_gp_evidence_grad (evidence_grad.hip) and ital_gp_loo_grad (loo_grad.hip) share,
 // in one place: the workspace layout, the prologue of five launches, the squared-distance tile, the walk over a wave's
-// lower-triangle elements, the k-major product tile, the serial sums that close the chains and the per-sample terms of lml and
-// the leave-one-out scores.  evidence_grad's factor, alpha, inverse diagonal, M and lml, and loo_grad's loo_logp and loo_mse,
+// lower-triangle elements, the serial sums that close the chains and the per-sample terms of lml and the leave-one-out
+// scores (the k-major product tile, tile_tn, is in mfma_tile.h).  evidence_grad's factor, alpha, inverse diagonal, M and lml, and loo_grad's loo_logp and loo_mse,
 // have evidence's bits because all run this code, not because files are kept in step.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -131,43 +131,7 @@ __device__ inline void for_each_lower(I iw, I jw, I n, F f) {
     }
 }
 
-// ------------------------------------------------------------------------------------- k-major product tile
-// acc[p][q] += sum over kbeg <= k < kend of A(k, r) B(k, c) for the 128 x 128 tile of a workgroup of 256 threads: wave
-// (wy, wx) owns tile rows 64 wy + 16 p + (kg + 4 reg) and tile columns 64 wx + 16 q + col (D layout of the f64 MFMA).
-// fa(k, r) / fb(k, c): the element of A at tile row r / of B at tile column c, both k-major; they return 0 outside their
-// operand (k at or past kend included).  Thread (k = tid / 16, tid % 16) stages eight runs of 16 columns of its k for each
-// operand, into the layout mfma_stage reads.  Register + LDS double buffer, one barrier per stage; ends with a barrier.
-template <class FA, class FB>
-__device__ inline void tile_tn(FA fa, FB fb, int kbeg, int kend, StageLds& lds, d4 acc[4][4]) {
-    const int kb = threadIdx.x >> 4, c16 = threadIdx.x & 15;
-    double ra[8], rb[8];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            ra[u] = fa(k0 + kb, c16 + 16 * u);
-            rb[u] = fb(k0 + kb, c16 + 16 * u);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            lds[buf][0][kb][c16 + 16 * u] = ra[u];
-            lds[buf][1][kb][c16 + 16 * u] = rb[u];
-        }
-    };
-    const int nstep = (kend - kbeg + KS - 1) / KS;
-    if (nstep <= 0) return;
-    fetch(kbeg);
-    stage(0);
-    __syncthreads();
-    for (int s_ = 0; s_ < nstep; s_++) {
-        const int buf = s_ & 1;
-        if (s_ + 1 < nstep) fetch(kbeg + (s_ + 1) * KS);
-        mfma_stage(lds, buf, acc);
-        if (s_ + 1 < nstep) stage(buf ^ 1);
-        __syncthreads();
-    }
-}
+// The k-major product tile (tile_tn) of gram_inverse_kernel and loo_grad lives in mfma_tile.h, next to tile_nt.
 
 // ----------------------------------------------------------------------------------------------------- serial sums
 constexpr double LOG2PI = 1.8378770664093454836;

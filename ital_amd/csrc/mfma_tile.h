@@ -4,6 +4,8 @@
 //   evidence.hip  gram_grid_kernel                                 (tile_nt)
 //   adapt.hip     inv_lm_kernel, inv_mt_kernel                     (its own tile_mm: predicated element functors, second operand
 //                                                                   k-major; it shares the constants, the LDS layout and mfma_stage)
+//   evidence_grad.hip, loo_grad.hip   gram_inverse_kernel and the W products   (tile_tn: both operands k-major behind predicates)
+//   influence.hip influence_tile_kernel                            (tile_tn: M^T V, both stored k-major)
 //
 // cov_block_lds_kernel (mcmi.hip), which this tile was taken from, keeps its own copy: its unit is in the include closures
 // that tools/stamp.py hashes and its code generation is pinned by goldens and stamped profiles.
@@ -103,6 +105,43 @@ __device__ inline void tile_nt(const double* const pa[4], const double* const pb
     for (int s_ = 0; s_ < nstep; s_++) {
         const int buf = s_ & 1;
         if (s_ + 1 < nstep) fetch((s_ + 1) * KS);
+        mfma_stage(lds, buf, acc);
+        if (s_ + 1 < nstep) stage(buf ^ 1);
+        __syncthreads();
+    }
+}
+
+// acc[p][q] += sum over kbeg <= k < kend of A(k, r) B(k, c) for the 128 x 128 tile of a workgroup of 256 threads: wave
+// (wy, wx) owns tile rows 64 wy + 16 p + (kg + 4 reg) and tile columns 64 wx + 16 q + col (D layout of the f64 MFMA).
+// fa(k, r) / fb(k, c): the element of A at tile row r / of B at tile column c, both k-major; they return 0 outside their
+// operand (k at or past kend included).  Thread (k = tid / 16, tid % 16) stages eight runs of 16 columns of its k for each
+// operand, into the layout mfma_stage reads.  Register + LDS double buffer, one barrier per stage; ends with a barrier.
+template <class FA, class FB>
+__device__ inline void tile_tn(FA fa, FB fb, int kbeg, int kend, StageLds& lds, d4 acc[4][4]) {
+    const int kb = threadIdx.x >> 4, c16 = threadIdx.x & 15;
+    double ra[8], rb[8];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            ra[u] = fa(k0 + kb, c16 + 16 * u);
+            rb[u] = fb(k0 + kb, c16 + 16 * u);
+        }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            lds[buf][0][kb][c16 + 16 * u] = ra[u];
+            lds[buf][1][kb][c16 + 16 * u] = rb[u];
+        }
+    };
+    const int nstep = (kend - kbeg + KS - 1) / KS;
+    if (nstep <= 0) return;
+    fetch(kbeg);
+    stage(0);
+    __syncthreads();
+    for (int s_ = 0; s_ < nstep; s_++) {
+        const int buf = s_ & 1;
+        if (s_ + 1 < nstep) fetch(kbeg + (s_ + 1) * KS);
         mfma_stage(lds, buf, acc);
         if (s_ + 1 < nstep) stage(buf ^ 1);
         __syncthreads();

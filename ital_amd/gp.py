@@ -430,6 +430,85 @@ class GaussianProcess(object):
         self._replicate_mean()
         return self
 
+    # ------------------------------------------------------------------ what a removal would change, without making it
+    def _influence_desc(self, mask=None):
+        """ital_influence_desc over this rank's state with its output tables; the tensors it points to ride along."""
+        lib = self._lib
+        need = int(lib.ital_gp_influence_workspace(self.m, self.n))
+        work = getattr(self, "_influence_work", None)
+        if work is None or work.numel() < need:
+            self._influence_work = work = torch.empty(need, dtype=torch.float64, device=self.device)
+        keep = dict(work=work, coef=torch.empty((self.m, 2), dtype=torch.float64, device=self.device),
+                    stats=torch.empty((self.m, 4), dtype=torch.float64, device=self.device),
+                    # a word of its own: a broken factor shows as NaN rows here and leaves the session's status alone
+                    status=torch.zeros(1, dtype=torch.int32, device=self.device), mask=mask)
+        d = _lib.ItalInfluenceDesc()
+        d.L, d.ldl, d.alpha, d.m = _ptr(self.L), self.cap, _ptr(self.alpha), self.m
+        d.V, d.ldv, d.n, d.mu, d.s2 = _ptr(self.V), self.ldv, self.n, _ptr(self.mu), _ptr(self.s2)
+        d.mask = _ptr(mask) if mask is not None else None
+        d.coef, d.stats, d.work, d.work_doubles, d.status = _ptr(keep["coef"]), _ptr(keep["stats"]), _ptr(work), work.numel(), \
+            _ptr(keep["status"])
+        return d, keep
+
+    def influence(self, mask=None):
+        """What taking each labelled sample back would change, for all of them in one pass over the whitened block
+        (ital_gp_influence: the product L^-1^T V on FP64 MFMA, nothing of size m x N stored, the state only read).  Returns a
+        dict of arrays in labelled order (the order of `ind`): c = diag K^-1, w = K^-1 y, loo_mean = y - w / c and
+        loo_var = 1 / c (R&W 5.12), and over the rows that `mask` (bool over all samples; None: all) counts: dmu_sq, the
+        summed squared change of the predictive mean; dmu_max, its largest absolute change; flips, the rows whose mean
+        changes sign; ds2, the total predictive variance the label removes.  A label whose c is not positive and finite (a
+        factor that was broken before) has NaN everywhere.  Several ranks: every rank makes the call; sums add, maxima take
+        the max."""
+        if self.m == 0:
+            raise RuntimeError("the GP has not been fitted: call fit()/update() first")
+        dmask = None
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.shape != (self.n_total,):
+                raise ValueError("mask must name every one of the %d samples" % self.n_total)
+            dmask = torch.from_numpy(np.ascontiguousarray(mask[self.row0:self.row1] != 0).astype(np.uint8)).to(self.device)
+            if dmask.numel() == 0:
+                dmask = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        d, keep = self._influence_desc(dmask)
+        check(self._lib.ital_gp_influence(ctypes.byref(d), _stream()))
+        coef = keep["coef"].cpu().numpy()
+        stats = keep["stats"]
+        if self.collective:
+            stats = sharding.all_gather_parts(stats.reshape(-1), [4 * self.m] * self.world, self.group)
+            parts = stats.cpu().numpy().reshape(self.world, self.m, 4)
+            stats = parts.sum(axis=0)
+            stats[:, 1] = parts[:, :, 1].max(axis=0)
+        else:
+            stats = stats.cpu().numpy()
+        c, w = coef[:, 0].copy(), coef[:, 1].copy()
+        y = np.asarray(self.y, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return dict(c=c, w=w, loo_mean=y - w / c, loo_var=1.0 / c, dmu_sq=stats[:, 0].copy(), dmu_max=stats[:, 1].copy(),
+                        flips=stats[:, 2].copy(), ds2=stats[:, 3].copy())
+
+    def preview_remove(self, ind):
+        """Predictive mean and variance of every sample as they would be after remove([i]), one row per listed labelled
+        sample i (data indices; each row is a removal of that sample alone), with no change of state: (mean[r, N], var[r, N]),
+        full length on every rank.  ValueError as remove() for an index without a label and for a query row."""
+        ind = [int(i) for i in ind]
+        pos_of = {i: p for p, i in enumerate(self.ind)}
+        for i in ind:
+            if i >= self.n_total:
+                raise ValueError("%d is a query row: queries cannot be removed" % i)
+            if i not in pos_of:
+                raise ValueError("sample %d has no label" % i)
+        r = len(ind)
+        if r == 0:
+            return np.zeros((0, self.n_total)), np.zeros((0, self.n_total))
+        d, keep = self._influence_desc()
+        mu_out = torch.zeros((r, self.ldv), dtype=torch.float64, device=self.device)
+        s2_out = torch.zeros((r, self.ldv), dtype=torch.float64, device=self.device)
+        sel = (ctypes.c_int * r)(*[pos_of[i] for i in ind])
+        check(self._lib.ital_gp_preview_remove(ctypes.byref(d), sel, r, _ptr(mu_out), _ptr(s2_out), self.ldv, _stream()))
+        mean = np.stack([self._full(mu_out[q]) for q in range(r)])
+        var = np.stack([self._full(s2_out[q]) for q in range(r)])
+        return mean, np.maximum(0, var)
+
     # ------------------------------------------------------------------ a live session: more rows, other hyper-parameters
     def _whiten_rows(self, row_start, n_rows, x_row_start=None):
         """xnorm, V[0:m], mu, s2 of the local rows [row_start, row_start + n_rows) against the whole current labelled set

@@ -120,6 +120,25 @@ class UnseenList(object):
         return self._flat
 
 
+def label_disagreement(label, loo_mean, loo_var):
+    """Probability that the model, fitted to all the OTHER labels, gives a labelled sample the opposite sign:
+    ndtr(-y * loo_mean / sqrt(loo_var)) of the leave-one-out predictive distribution (R&W 5.12)."""
+    from scipy.special import ndtr
+    label, loo_mean, loo_var = (np.asarray(a, dtype=np.float64) for a in (label, loo_mean, loo_var))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return ndtr(-label * loo_mean / np.sqrt(loo_var))
+
+
+def mistake_posterior(disagreement, q):
+    """Posterior probability that a label is a slip, from the prior flip probability q and the disagreement d of the other
+    labels with it: q d / (q d + (1 - q)(1 - d)).  None without a prior in (0, 1)."""
+    if q is None or not (0.0 < float(q) < 1.0):
+        return None
+    q, d = float(q), np.asarray(disagreement, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return q * d / (q * d + (1.0 - q) * (1.0 - d))
+
+
 class ActiveRetrievalBase(object):
 
     #: initial capacity of the labelled set on the device (None: GaussianProcess picks it; it grows on demand)
@@ -344,6 +363,69 @@ class ActiveRetrievalBase(object):
             self.unnameable_ids.discard(i)
         self.__dict__["_unseen"] = None
         self._fitted = self.gp.m > 0
+
+    def audit(self, mistake_prob=None, unseen_only=True):
+        """Which labels deserve a second look, and what taking each of them back would change -- for all labelled data
+        samples in one pass on the device (GaussianProcess.influence), with no change of state; what clone() + revoke([i])
+        per label answers with m copies of the whitened block.  Query rows are left out: they cannot be revoked.  Returns a
+        dict of arrays over the labelled data samples in labelled order: ids; label (+1 / -1); loo_mean, loo_var, the
+        prediction for the sample from all the other labels; disagreement, the probability that this prediction has the
+        opposite sign; p_mistake, its posterior with the prior flip probability `mistake_prob` (default: the learner's own
+        `mistake_prob` when it has one in (0, 1); else None); dmu_rms, dmu_max, flips, ds2: root mean square and maximum
+        of the change of the predictive mean, number of rows whose mean changes sign and total variance the label removes,
+        over the unseen samples (`unseen_only`, the rows a user still acts on) or over every data row; order, the positions
+        sorted by disagreement, largest first, ties by position.  RuntimeError before any feedback.  Several ranks: every
+        rank makes the call."""
+        gp = self.gp
+        n = self._num_samples()
+        pos = [p for p, i in enumerate(gp.ind) if i < n] if self._fitted else []
+        if not pos:
+            raise RuntimeError("audit() needs feedback: call update() first")
+        mask = None
+        counted = n
+        if unseen_only:
+            unseen = self._unseen_array()
+            mask = np.zeros(n, dtype=bool)
+            mask[unseen] = True
+            counted = len(unseen)
+        inf = gp.influence(mask)
+        pos = np.asarray(pos, dtype=np.int64)
+        label = np.asarray(gp.y, dtype=np.float64)[pos]
+        loo_mean, loo_var = inf["loo_mean"][pos], inf["loo_var"][pos]
+        d = label_disagreement(label, loo_mean, loo_var)
+        q = mistake_prob if mistake_prob is not None else getattr(self, "mistake_prob", None)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rms = np.sqrt(inf["dmu_sq"][pos] / counted) if counted else np.zeros(len(pos))
+        return dict(ids=np.asarray(gp.ind, dtype=np.int64)[pos], label=label, loo_mean=loo_mean, loo_var=loo_var,
+                    disagreement=d, p_mistake=mistake_posterior(d, q), dmu_rms=rms, dmu_max=inf["dmu_max"][pos],
+                    flips=inf["flips"][pos], ds2=inf["ds2"][pos], order=np.argsort(-d, kind="stable"))
+
+    def preview_revoke(self, ids):
+        """(rel_mean, var) of every sample as they would be after revoke([i]), one row per id (each row takes that id alone
+        back), with no change of state (GaussianProcess.preview_remove).  ValueError for an id that never got feedback; an
+        unnameable id has no label to lose, its row is the current state."""
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if not (i in self.relevant_ids or i in self.irrelevant_ids or i in self.unnameable_ids):
+                raise ValueError("sample %d never got feedback" % i)
+        labelled = [i for i in ids if i in self.relevant_ids or i in self.irrelevant_ids]
+        n = self._num_samples()
+        mean, var = np.empty((len(ids), n)), np.empty((len(ids), n))
+        if labelled:
+            lm, lv = self.gp.preview_remove(labelled)
+        if len(labelled) < len(ids):
+            if self._fitted:
+                cm, cv = self.gp.predict_stored(cov_mode='diag')
+            else:
+                cm, cv = np.zeros(n), np.full(n, float(self.var))
+        at = 0
+        for q, i in enumerate(ids):
+            if i in self.relevant_ids or i in self.irrelevant_ids:
+                mean[q], var[q] = lm[at], lv[at]
+                at += 1
+            else:
+                mean[q], var[q] = cm, cv
+        return mean, var
 
     def _start_afresh(self):
         """What a learner derives from the data matrix or the hyper-parameters and keeps between rounds -- the cached list of
