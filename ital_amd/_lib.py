@@ -1,6 +1,7 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
 include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_evidence_grad.h,
-include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h and include/ital_cosine.h).
+include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h, include/ital_cosine.h and
+include/ital_reweigh.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -216,6 +217,20 @@ REVOKE_SIGNATURES = {
 }
 
 
+class ItalReweighDesc(ctypes.Structure):
+    """ital_reweigh_desc (include/ital_reweigh.h): the GP state and the labelled positions whose diagonal entry changes."""
+    _fields_ = [("L", c_void_p), ("ldl", c_int), ("alpha", c_void_p), ("V", c_void_p), ("ldv", c_int64), ("n", c_int64),
+                ("mu", c_void_p), ("s2", c_void_p), ("m", c_int), ("work", c_void_p), ("work_doubles", c_int64),
+                ("status", c_void_p), ("r", c_int), ("pos", c_void_p), ("delta", c_void_p)]
+
+
+#: per-label noise by Cholesky up- and downdates, declared in include/ital_reweigh.h
+REWEIGH_SIGNATURES = {
+    "ital_gp_reweigh": (c_int, [ctypes.POINTER(ItalReweighDesc), c_void_p]),
+    "ital_gp_reweigh_workspace": (c_int64, [c_int, c_int]),
+}
+
+
 class ItalInfluenceDesc(ctypes.Structure):
     """ital_influence_desc (include/ital_influence.h): the GP state that is read, the row mask and where the tables go."""
     _fields_ = [("L", c_void_p), ("ldl", c_int), ("alpha", c_void_p), ("m", c_int), ("V", c_void_p), ("ldv", c_int64),
@@ -378,7 +393,7 @@ def load(path=LIB_PATH):
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
             list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()) + list(INFLUENCE_SIGNATURES.items()) + \
-            list(CTX_AUDIT_SIGNATURES.items()):
+            list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

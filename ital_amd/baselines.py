@@ -192,7 +192,9 @@ class EMOC(ActiveRetrievalBase):
                 E = torch.zeros((m, nq), dtype=torch.float64, device=dev)
                 E[qpos, list(range(nq))] = 1.0
                 Vq = torch.zeros((m, _pad16(nq)), dtype=torch.float64, device=dev)
-                Vq[:, :nq] = Lm.t()[:, qpos] - float(gp.noise) * torch.linalg.solve_triangular(Lm, E, upper=False)
+                # what leaves the diagonal is the noise of that position: the scalar plus its label's own (GaussianProcess.reweigh)
+                own = torch.from_numpy(float(gp.noise) + gp.label_noise[qpos]).to(dev)
+                Vq[:, :nq] = Lm.t()[:, qpos] - torch.linalg.solve_triangular(Lm, E, upper=False) * own[None, :]
                 Xq, qn = gp.XT[qpos].contiguous(), gp.XTn[qpos].contiguous()
                 check(lib.ital_cov_abs_rowsum(_ptr(gp.Xd), _ptr(gp.xnorm), gp.n, _ptr(Xq), _ptr(qn), nq, gp.ldx,
                                               _ptr(gp.V), gp.ldv, _ptr(Vq), Vq.shape[1], m, float(self.var),

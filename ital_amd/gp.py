@@ -5,7 +5,7 @@ ind, y, X, length_scale, var, noise) but a different state: the reference stores
 `K_all` (gp.py:128) and an explicit inverse re-computed at every update (gp.py:194); this class keeps, per
 GPU, the row shard of X and the Cholesky-whitened block
 
-    L L^T = K[T,T] + noise*I,   V = L^-1 K[T,:]  (m x n, one contiguous n-vector per labelled point),
+    L L^T = K[T,T] + noise*I + diag(label_noise),   V = L^-1 K[T,:]  (m x n, one contiguous n-vector per labelled point),
     mu = V^T alpha (alpha = L^-1 y),   s2 = var - colsum(V^2)          
 
 so an update appends c rows (rank-c Cholesky append) and N never appears squared.  All arithmetic runs in
@@ -245,6 +245,7 @@ class GaussianProcess(object):
         self.y = None
         self.m = 0
         self.appends = []          # sizes of the update() calls that built the labelled set (state_dict / replay)
+        self.label_noise = np.zeros(0)       # extra noise variance of every labelled sample, aligned with ind (reweigh)
         self.mu = torch.zeros(max(self.n, 1), dtype=torch.float64, device=self.device)
         self.s2 = torch.full((max(self.n, 1),), float(self.var), dtype=torch.float64, device=self.device)
         self.mu_all = torch.zeros(self.n_total, dtype=torch.float64, device=self.device) if self.collective else self.mu[: self.n]
@@ -281,6 +282,7 @@ class GaussianProcess(object):
             self._append(self._gather_rows(ind), y)
         self.ind += ind
         self.y = y.copy() if self.y is None else np.concatenate((self.y, y))
+        self.label_noise = np.concatenate((self.label_noise, np.zeros(len(ind))))
         self.appends.append(len(ind))
         t1 = time.perf_counter() if hc is not None else 0.0
         self._replicate_mean()
@@ -299,6 +301,7 @@ class GaussianProcess(object):
         self._append(rows, y)
         self.ind += list(ind) if ind is not None else list(range(self.n_total + self.m - len(y), self.n_total + self.m))
         self.y = y.copy() if self.y is None else np.concatenate((self.y, y))
+        self.label_noise = np.concatenate((self.label_noise, np.zeros(len(y))))
         self.appends.append(-len(y))          # negative: feature vectors that are not rows of the data (queries)
         self._replicate_mean()
         return self
@@ -424,11 +427,82 @@ class GaussianProcess(object):
             self.appends = appends_after_remove(self.appends, p)
             del self.ind[p]
             self.y = np.delete(self.y, p)
+            self.label_noise = np.delete(self.label_noise, p)
             self.m -= 1
         if self.m == 0:
             self.reset()              # nothing is left: the prior, exactly (the kernels left rows >= m of V, L, XT zero)
         self._replicate_mean()
         return self
+
+    # ------------------------------------------------------------------ trusting a label less, without taking it back
+    def _reweigh_call(self, L, alpha, status, pos, delta, factor_only=False):
+        """One ital_gp_reweigh call over the factor (L, alpha) -- and, unless `factor_only`, this rank's V, mu, s2 -- for the
+        labelled positions `pos` (strictly increasing) whose diagonal entry changes by `delta`; `status`: the word it may
+        set.  The host arrays are read before the call returns."""
+        lib, r = self._lib, len(pos)
+        need = int(lib.ital_gp_reweigh_workspace(self.m, r))
+        work = getattr(self, "_reweigh_work", None)
+        if work is None or work.numel() < need:
+            self._reweigh_work = work = torch.empty(need, dtype=torch.float64, device=self.device)
+        d = _lib.ItalReweighDesc()
+        d.L, d.ldl, d.alpha, d.m = _ptr(L), self.cap, _ptr(alpha), self.m
+        if factor_only:
+            d.V, d.ldv, d.n, d.mu, d.s2 = None, 0, 0, None, None
+        else:
+            d.V, d.ldv, d.n, d.mu, d.s2 = _ptr(self.V), self.ldv, self.n, _ptr(self.mu), _ptr(self.s2)
+        d.work, d.work_doubles, d.status, d.r = _ptr(work), work.numel(), _ptr(status), r
+        cpos = (ctypes.c_int * r)(*[int(p) for p in pos])
+        cdelta = (ctypes.c_double * r)(*[float(v) for v in delta])
+        d.pos, d.delta = ctypes.cast(cpos, ctypes.c_void_p), ctypes.cast(cdelta, ctypes.c_void_p)
+        check(lib.ital_gp_reweigh(ctypes.byref(d), _stream()))
+
+    def reweigh(self, ind, extra):
+        """Sets the extra noise variance of labelled samples (data indices `ind`; `extra`: one value >= 0 for all of them or
+        one per index): the model becomes the GP on K_TT + noise I + diag(label_noise), with labels, labelled order and
+        `appends` as they are.  The value is absolute -- a call sets it, 0 is a label of full weight again, a large one
+        approaches remove([i]).  The factor's trailing block goes through one rank-one update or downdate per changed
+        label and V through ONE sweep for up to eight of them (ital_gp_reweigh); no feature row is read.  Every rank makes
+        the same call.  The reference has nothing like it: its noise is one scalar (gp.py:156).
+
+        ValueError (nothing is changed) for an index that has no label, one named twice, a query row, a negative or
+        non-finite value.  An empty list, or values that all equal the present ones, is a no-op without a launch.
+        LinAlgError when the device refused (a pivot of the downdate was not positive): the model is then as it was."""
+        ind = [int(i) for i in ind]
+        extra = np.asarray(extra, dtype=np.float64)
+        if extra.ndim == 0:
+            extra = np.full(len(ind), float(extra))
+        extra = extra.reshape(-1)
+        if len(extra) != len(ind):
+            raise ValueError("ind and extra differ in length")
+        if not np.all(np.isfinite(extra)) or np.any(extra < 0):
+            raise ValueError("the extra noise of a label must be finite and >= 0")
+        if len(set(ind)) != len(ind):
+            raise ValueError("a sample is named twice")
+        pos_of = {i: p for p, i in enumerate(self.ind)}
+        for i in ind:
+            if i >= self.n_total:
+                raise ValueError("%d is a query row: queries keep their full weight" % i)
+            if i not in pos_of:
+                raise ValueError("sample %d has no label" % i)
+        changes = sorted((pos_of[i], float(v)) for i, v in zip(ind, extra) if float(v) != self.label_noise[pos_of[i]])
+        if not changes:
+            return self
+        pos = [p for p, _ in changes]
+        delta = [v - float(self.label_noise[p]) for p, v in changes]
+        with torch.cuda.device(self.device):
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)     # the call's own word: a refusal changes nothing
+            self._reweigh_call(self.L, self.alpha, status, pos, delta)
+            self.check_status(int(status.item()))
+            for p, v in changes:
+                self.label_noise[p] = v
+            self._replicate_mean()
+        return self
+
+    def _no_label_noise(self, what):
+        """ValueError while any label carries extra noise: `what` rebuilds Grams from XT with the scalar noise alone."""
+        if np.any(self.label_noise != 0):
+            raise ValueError("%s does not know the per-label noise of this session yet: clear it first with "
+                             "set_label_noise / reweigh(ind, 0)" % what)
 
     # ------------------------------------------------------------------ what a removal would change, without making it
     def _influence_desc(self, mask=None):
@@ -766,10 +840,11 @@ class GaussianProcess(object):
                              "(ital_amd.DeviceData(data)) instead of a numpy array")
         g = object.__new__(GaussianProcess)
         g.__dict__.update(self.__dict__)
-        for name in ("_append_desc", "_ybuf", "_remove_work", "_topk_work", "host_clock"):
+        for name in ("_append_desc", "_ybuf", "_remove_work", "_reweigh_work", "_topk_work", "host_clock"):
             g.__dict__.pop(name, None)
         g.ind, g.appends = list(self.ind), list(self.appends)
         g.y = None if self.y is None else self.y.copy()
+        g.label_noise = self.label_noise.copy()
         with torch.cuda.device(self.device):
             g.V = torch.zeros_like(self.V)
             if self.m:
@@ -784,8 +859,9 @@ class GaussianProcess(object):
         """Other kernel hyper-parameters for a live model (None: as it is), e.g. what ital_amd.tune found: the factor and alpha
         are built anew in fresh buffers (ital_chol_append over the stored XT, y in blocks of 16) and, once the status word
         says the Gram was positive definite, swapped in; every local row is then whitened again (ital_whiten_rows) and the
-        means replicated -- every rank makes the same call.  LinAlgError leaves the model exactly as it was.  What the
-        parent offered instead: set the attributes and fit(ind, y), i.e. ceil(m/16) sweeps over X and V."""
+        means replicated -- every rank makes the same call.  The per-label noise of reweigh() stays: it goes onto the new
+        factor by one factor-only ital_gp_reweigh call before the swap.  LinAlgError leaves the model exactly as it was.
+        What the parent offered instead: set the attributes and fit(ind, y), i.e. ceil(m/16) sweeps over X and V."""
         ls = float(self.length_scale if length_scale is None else length_scale)
         var = float(self.var if var is None else var)
         noise = float(self.noise if noise is None else noise)
@@ -804,6 +880,9 @@ class GaussianProcess(object):
                     c = min(16, m - c0)
                     check(lib.ital_chol_append(_ptr(self.XT), _ptr(self.XTn), self.ldx, _ptr(L), self.cap, _ptr(alpha),
                                                _ptr(yd[c0:c0 + c]), c0, c, var, ls, noise, _ptr(status), st))
+                pos = [int(p) for p in np.flatnonzero(self.label_noise)]
+                if pos:                       # the per-label noise on top, factor only: the rows are whitened below anyway
+                    self._reweigh_call(L, alpha, status, pos, [float(self.label_noise[p]) for p in pos], factor_only=True)
                 self.check_status(int(status.item()))
                 self.L, self.alpha = L, alpha
                 self._append_desc = None      # it holds L and alpha
@@ -822,6 +901,7 @@ class GaussianProcess(object):
         download(out, g0, c), which copies the first c candidates' results to out[...][g0:g0 + c]."""
         if self.m == 0:
             raise RuntimeError("the GP has not been fitted")
+        self._no_label_noise("the evidence family (evidence, evidence_grad, loo_grad, tune_params, fit_params, session_scores)")
         prm = _candidate_params(self, params_list)
         G, m, dev = len(prm), self.m, self.device
         out = {k: np.empty((G,) + s) for k, s in shapes.items()}

@@ -199,15 +199,20 @@ class ActiveRetrievalBase(object):
         mvndst stream and the state of numpy's global legacy generator (what MCMI_min(subsample), the change-estimation
         subset and the Monte-Carlo switches draw from, as the reference does).  Small (O(labelled samples)): the whitened
         block V is rebuilt on load, not stored -- the replay appends sample by sample where the session appended staged
-        batches, so the means agree to ~1e-15, not bit for bit (a pick at an exact numerical tie may differ)."""
+        batches, so the means agree to ~1e-15, not bit for bit (a pick at an exact numerical tie may differ).  The entry
+        `label_noise` (set_label_noise; aligned with `ind`) is there only when some label carries extra noise."""
         from . import mvn_stream
         gp = self.gp
-        return dict(version=1, n=self._num_samples(), hyper=(float(self.length_scale), float(self.var), float(self.noise)),
-                    ind=[int(i) for i in gp.ind], y=(gp.y.copy() if gp.y is not None else np.zeros(0)),
-                    appends=list(gp.appends), relevant_ids=sorted(self.relevant_ids),
-                    irrelevant_ids=sorted(self.irrelevant_ids), unnameable_ids=sorted(self.unnameable_ids),
-                    rounds=int(self.rounds), mvn_stream=(tuple(mvn_stream.GLOBAL.state), int(mvn_stream.GLOBAL.draws)),
-                    np_random=np.random.get_state())
+        sd = dict(version=1, n=self._num_samples(), hyper=(float(self.length_scale), float(self.var), float(self.noise)),
+                  ind=[int(i) for i in gp.ind], y=(gp.y.copy() if gp.y is not None else np.zeros(0)),
+                  appends=list(gp.appends), relevant_ids=sorted(self.relevant_ids),
+                  irrelevant_ids=sorted(self.irrelevant_ids), unnameable_ids=sorted(self.unnameable_ids),
+                  rounds=int(self.rounds), mvn_stream=(tuple(mvn_stream.GLOBAL.state), int(mvn_stream.GLOBAL.draws)),
+                  np_random=np.random.get_state())
+        if np.any(gp.label_noise != 0):
+            # only a session with weighted labels has the entry: every other dict is what it was before there were any
+            sd["label_noise"] = gp.label_noise.copy()          # aligned with ind
+        return sd
 
     def load_state_dict(self, sd, restore_stream=True):
         """Restores a session saved by state_dict() on a learner constructed over the same data (and queries) with the same
@@ -231,6 +236,13 @@ class ActiveRetrievalBase(object):
             at += c
         if self.gp.ind != ind:
             raise ValueError("state_dict does not match this learner's queries")
+        extra = sd.get("label_noise")
+        if extra is not None:
+            extra = np.asarray(extra, dtype=np.float64).reshape(-1)
+            if len(extra) != len(ind):
+                raise ValueError("state_dict's label_noise does not match its labelled set")
+            pos = np.flatnonzero(extra)
+            self.gp.reweigh([ind[p] for p in pos], extra[pos])
         self.relevant_ids = set(sd["relevant_ids"])
         self.irrelevant_ids = set(sd["irrelevant_ids"])
         self.unnameable_ids = set(sd["unnameable_ids"])
@@ -363,6 +375,28 @@ class ActiveRetrievalBase(object):
             self.unnameable_ids.discard(i)
         self.__dict__["_unseen"] = None
         self._fitted = self.gp.m > 0
+
+    def set_label_noise(self, noise_by_id):
+        """Keeps labels but trusts them less: `noise_by_id` maps ids with feedback to the extra noise variance (>= 0) their
+        label carries from now on (GaussianProcess.reweigh: Cholesky up- and downdates and one sweep on the device).  The
+        value is absolute; 0 gives a label its full weight back, a large one approaches revoke([id]).  The id sets, the unseen
+        list, `rounds` and both random streams stay as they are; the prepared next round and the batch state of the last
+        fetch are dropped.  ValueError (nothing changed) for an id that is neither relevant nor irrelevant -- an unnameable
+        one has no label -- and for a negative or non-finite value.  Several ranks: every rank makes the same call."""
+        ids = [int(i) for i in noise_by_id]
+        for i in ids:
+            if not (i in self.relevant_ids or i in self.irrelevant_ids):
+                raise ValueError("sample %d has no label" % i)
+        self.gp.reweigh(ids, [float(noise_by_id[i]) for i in noise_by_id])
+        self._last_batch = None
+        rb = getattr(self, "_round_bufs", None)
+        if rb is not None:
+            rb.drop_prepared()
+
+    def label_noise(self):
+        """{id: extra noise variance} of the labels that carry some (set_label_noise)."""
+        gp = self.gp
+        return {int(gp.ind[p]): float(gp.label_noise[p]) for p in np.flatnonzero(gp.label_noise)}
 
     def audit(self, mistake_prob=None, unseen_only=True):
         """Which labels deserve a second look, and what taking each of them back would change -- for all labelled data
