@@ -1,7 +1,7 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
 include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_evidence_grad.h,
-include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h, include/ital_cosine.h and
-include/ital_reweigh.h).
+include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h, include/ital_cosine.h,
+include/ital_reweigh.h and include/ital_knn.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -370,6 +370,16 @@ COSINE_SIGNATURES = {
 }
 
 
+#: the k nearest neighbours of rows of a store among its rows, declared in include/ital_knn.h
+KNN_MAX_K, KNN_MAX_SPLITS, KNN_AUTO_SPLITS = 32, 64, 16
+KNN_METRICS = {"cosine": 0, "sqeuclidean": 1}
+KNN_SIGNATURES = {
+    "ital_knn_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "ital_knn_workspace": (ctypes.c_size_t, [c_int64, c_int, c_int]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -393,7 +403,7 @@ def load(path=LIB_PATH):
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
             list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()) + list(INFLUENCE_SIGNATURES.items()) + \
-            list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()):
+            list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

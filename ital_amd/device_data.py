@@ -181,6 +181,96 @@ def compact_rows(X, xnorm, n, keep, X_dst, xnorm_dst, status=None):
                                        0 if status is None else status.data_ptr(), _stream()))
 
 
+# ---------------------------------------------------------------------------------------------------- neighbour lists
+def _knn_args(k, metric):
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError("metric must be one of %s, not %r" % (sorted(_lib.KNN_METRICS), metric))
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _lib.KNN_MAX_K:
+        raise ValueError("k must be an integer in 1..%d, not %r" % (_lib.KNN_MAX_K, k))
+    return int(k), _lib.KNN_METRICS[metric]
+
+
+def knn_rows(X, xnorm, n, q, c, metric, k, skip_self, idx, dist, rowsum=None, accumulate=False, splits=0):
+    """The rows q = (q0, q1) of idx / dist (and rowsum) <- the k nearest of the query rows [q0, q1) among the rows
+    c = (c0, c1) of the n padded device rows X with squared norms xnorm, on the current stream (ital_knn_rows).  idx: [n, k]
+    int64, dist: [n, k] float64, rowsum: [n] float64 or None, all contiguous.  The workspace lives until the call returns; the
+    caching allocator keeps it for the stream's work."""
+    q0, q1 = q
+    nq = q1 - q0
+    if nq <= 0:
+        return
+    lib = _lib.lib()
+    bytes_ = lib.ital_knn_workspace(nq, k, splits)
+    work = torch.empty(max(bytes_, 8), dtype=torch.uint8, device=X.device)
+    check(lib.ital_knn_rows(X.data_ptr(), DTYPE_CODES[X.dtype], xnorm.data_ptr(), n, X.shape[1], q0, q1, c[0], c[1],
+                            _lib.KNN_METRICS[metric] if isinstance(metric, str) else metric, k, int(bool(skip_self)),
+                            int(bool(accumulate)), splits, dist[q0:].data_ptr(), idx[q0:].data_ptr(),
+                            0 if rowsum is None else rowsum[q0:].data_ptr(), work.data_ptr(), bytes_, _stream()))
+
+
+class NeighbourLists(object):
+    """The k nearest neighbours of the first n rows of one storage tensor, with the sums of their distances: what a store (or
+    a learner on plain numpy data) keeps per (metric, k, skip_self).  `grow` takes in rows appended to the same storage by two
+    accumulating calls -- old rows against the new data range, new rows against everything -- which by the definition of
+    ital_knn_rows give the bits of a fresh computation."""
+
+    def __init__(self, X, xnorm, n, metric, k, skip_self):
+        self.metric, self.k, self.skip_self = metric, k, bool(skip_self)
+        self.X, self.n = X, 0          # the storage is held: its address cannot come back under other rows
+        self.idx = self.dist = self.rowsum = None
+        self.density = None           # (sum - 1) / (k - 1): made on demand by neighbour_density
+        self.grow(X, xnorm, n)
+
+    def serves(self, X, n):
+        return X.data_ptr() == self.X.data_ptr() and n == self.n
+
+    def extends(self, X, n):
+        return X.data_ptr() == self.X.data_ptr() and n > self.n
+
+    def grow(self, X, xnorm, n):
+        old = self.n
+        with torch.cuda.device(X.device):
+            idx = torch.empty((max(n, 1), self.k), dtype=torch.int64, device=X.device)
+            dist = torch.empty((max(n, 1), self.k), dtype=torch.float64, device=X.device)
+            rowsum = torch.empty(max(n, 1), dtype=torch.float64, device=X.device)
+            if old:
+                idx[:old], dist[:old] = self.idx[:old], self.dist[:old]
+                knn_rows(X, xnorm, n, (0, old), (old, n), self.metric, self.k, self.skip_self, idx, dist, rowsum, accumulate=True)
+            knn_rows(X, xnorm, n, (old, n), (0, n), self.metric, self.k, self.skip_self, idx, dist, rowsum)
+        self.idx, self.dist, self.rowsum, self.n, self.density = idx, dist, rowsum, n, None
+
+    def densities(self):
+        """(rowsum - 1.0) / (k - 1) per row, the reference's expression (baseline_methods.py:469) with K = k - 1: one FP64
+        subtraction and one FP64 division."""
+        if self.density is None:
+            self.density = (self.rowsum[: self.n] - 1.0) / float(self.k - 1)
+        return self.density
+
+
+def neighbour_lists(cache, X, xnorm, n, metric, k, skip_self):
+    """The NeighbourLists of the first n rows of X from the dict `cache`: served when they were built for this storage and
+    row count, grown when the same storage holds more rows now, built afresh otherwise (never a list that looks past n)."""
+    key = (metric, k, bool(skip_self))
+    kept = cache.get(key)
+    if kept is not None and kept.serves(X, n):
+        return kept
+    if kept is not None and kept.extends(X, n):
+        kept.grow(X, xnorm, n)
+        return kept
+    cache[key] = NeighbourLists(X, xnorm, n, metric, k, skip_self)
+    return cache[key]
+
+
+def check_density_k(K, n):
+    if isinstance(K, bool) or int(K) != K or int(K) < 1:
+        raise ValueError("K must be a positive integer, not %r" % (K,))
+    if K + 1 > n:
+        raise ValueError("K + 1 = %d neighbours (self included) of %d rows" % (K + 1, n))
+    if K + 1 > _lib.KNN_MAX_K:
+        raise ValueError("K + 1 = %d is above the %d neighbours ital_knn_rows keeps" % (K + 1, _lib.KNN_MAX_K))
+    return int(K)
+
+
 class DeviceData(object):
     """n x d feature rows on `device` as padded rows `X` [n, ldx] -- FP64, or the source's own element type -- and FP64
     squared norms `xnorm` [n].
@@ -216,6 +306,8 @@ class DeviceData(object):
         #: the change log: ("append", k) and ("remove", ascending removed ids, n before) in order; `epoch` == len(log).  A
         #: learner remembers the epoch it has seen and walks the log from there (GaussianProcess.sync_data).
         self.log, self.epoch = [], 0
+        #: neighbour lists per (metric, k, skip_self) (NeighbourLists): shared by every learner on this store
+        self._knn = {}
         self._alloc(max(int(t.shape[0]), int(capacity or 0), 1))
         self._write(t)
 
@@ -228,6 +320,9 @@ class DeviceData(object):
                 # the tensors left behind are not freed here: a learner that still views them keeps them, and its prefix
                 X[: self.n] = self._X[: self.n]
                 xnorm[: self.n] = self._xnorm[: self.n]
+                for kept in self._knn.values():        # the same rows at a new address: the lists stay and can still grow
+                    if kept.X.data_ptr() == self._X.data_ptr():
+                        kept.X = X
         self._X, self._xnorm, self.capacity = X, xnorm, int(capacity)
 
     def _write(self, t):
@@ -286,6 +381,39 @@ class DeviceData(object):
         sel = torch.from_numpy(idx % max(self.n, 1)).to(self.device)
         return self._X[: self.n].index_select(0, sel)[:, : self.d].to(torch.float64).cpu().numpy()
 
+    # ------------------------------------------------------------------ neighbour lists
+    def _view(self, view):
+        """(X, xnorm, n) of the store, or of a learner's own prefix `view` = (X, xnorm, n) of it."""
+        return (self._X, self._xnorm, self.n) if view is None else view
+
+    def knn(self, k, metric="cosine", skip_self=True, rows=None):
+        """The k nearest rows of every row -- or of the rows `rows`, a range or a list of indices -- as device tensors
+        (idx int64 [q, k], dist float64 [q, k]): ital_knn_rows (include/ital_knn.h, where distance and order are defined; slots
+        beyond the available rows hold -1 / +inf).  metric: "cosine" or "sqeuclidean".  The lists of all rows are computed once
+        per (metric, k, skip_self) and kept on the store; after append() the next request extends them, remove() drops them.
+        The tensors returned without `rows` are the kept ones: do not write to them.  ValueError for k outside 1..32 or an
+        unknown metric."""
+        k, _ = _knn_args(k, metric)
+        kept = neighbour_lists(self._knn, self._X, self._xnorm, self.n, metric, k, skip_self)
+        if rows is None:
+            return kept.idx[: self.n], kept.dist[: self.n]
+        if isinstance(rows, range) and rows.step == 1 and 0 <= rows.start <= rows.stop <= self.n:
+            return kept.idx[rows.start:rows.stop], kept.dist[rows.start:rows.stop]
+        sel = np.asarray(list(rows), dtype=np.int64).reshape(-1)
+        if len(sel) and (sel.min() < -self.n or sel.max() >= self.n):
+            raise IndexError("row index outside the %d rows" % self.n)
+        sel = torch.from_numpy(sel % max(self.n, 1)).to(self.device)
+        return kept.idx.index_select(0, sel), kept.dist.index_select(0, sel)
+
+    def neighbour_density(self, K, view=None):
+        """The device vector (sum of the cosine distances to the K + 1 nearest rows, the row itself included, - 1.0) / K: the
+        density of the reference's SUD (baseline_methods.py:469) with its `- 1.0`, which makes the density of a tight
+        neighbourhood negative.  Kept on the store and shared by every learner on it; `view`: a learner's own (X, xnorm, n),
+        for one that has not caught up with the store.  ValueError if K + 1 > n or K + 1 > 32."""
+        X, xnorm, n = self._view(view)
+        K = check_density_k(K, n)
+        return neighbour_lists(self._knn, X, xnorm, n, "cosine", K + 1, False).densities()
+
     def append(self, rows):
         """Adds rows (the input kinds of the constructor) as rows n .. n + k - 1 and returns k.  ValueError, with nothing
         changed, for another number of columns.  Within the capacity the rows are written in place -- rows >= n are read by
@@ -319,6 +447,7 @@ class DeviceData(object):
             xnorm = torch.empty(self.capacity, dtype=torch.float64, device=self.device)
             compact_rows(self._X, self._xnorm, self.n, keep_d, X, xnorm)       # the ids were checked on the host
         self._X, self._xnorm, self.n = X, xnorm, len(keep)
+        self._knn = {}                                  # the lists may name removed rows
 
     def remove(self, ids):
         """Deletes rows like np.delete(X, ids, axis=0): the survivors keep their order and get the indices 0 .. n - r - 1.
