@@ -289,6 +289,33 @@ def test_full_size_against_scipy():
             assert abs(average_precision_score(rel[rows[te]], got) - average_precision_score(rel[rows[te]], want)) <= 1e-9
 
 
+def test_held_out_scores_where_a_workgroup_walks_two_tiles():
+    """4200 rows, d = 5, two folds: the kernel-times-W pass of _predict runs ital_kernel_matvec at (4200, 4200), where kw_split
+    gives every workgroup a chunk of two 128-wide tiles (17 splits) -- the loop the Iris-sized goldens never enter."""
+    import sys
+    from scipy.linalg import cho_factor, cho_solve
+    from ital_amd import tune
+    sys.path.insert(0, HERE)
+    import _dense_ref
+    n = 4200
+    assert _dense_ref.expected_split(n, n) == (17, 2)
+    rng = np.random.default_rng(4200)
+    X = rng.random((n, 5))
+    rel = np.where(X[:, 0] + 0.3 * rng.standard_normal(n) > 0.5, 1, -1)
+    ls, var, noise = 0.5, 1.0, 1e-2
+    rows, folds, out = tune.held_out_scores(X, rel, dict(length_scale=ls, var=var, noise=noise), n_folds=2)
+    assert out is not None and out.shape == (n, 2) and len(rows) == n
+    for f, (tr, te) in enumerate(folds):
+        A, B = X[rows[tr]], X[rows[te]]
+        K = _rbf(A, A, ls, var) + noise * np.eye(len(tr))
+        want = _rbf(B, A, ls, var) @ cho_solve(cho_factor(K, lower=True), rel[rows[tr]].astype(np.float64))
+        cond = np.linalg.cond(K, 1)
+        err = np.max(np.abs(out[rows[te], f] - want))
+        print("fold %d: cond_1 = %.3g, max |score| = %.3g, max error = %.3g, bound = %.3g"
+              % (f, cond, np.max(np.abs(want)), err, _bound(cond, np.max(np.abs(want)))))
+        assert err <= _bound(cond, np.max(np.abs(want)))
+
+
 def test_not_positive_definite_scores_minus_inf():
     from ital_amd import tune
     rng = np.random.default_rng(11)
