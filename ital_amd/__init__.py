@@ -8,7 +8,7 @@ The arithmetic lives in hand-written HIP kernels (ital_amd/csrc, C ABI in includ
 from . import mvn_stream
 from .mvn_stream import GLOBAL as mvn_global_stream
 
-__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "SUD", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode"]
+__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "SUD", "USDM", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode"]
 
 
 def serving_mode():
@@ -44,6 +44,9 @@ def __getattr__(name):
     if name == "SUD":
         from .sud import SUD
         return SUD
+    if name == "USDM":
+        from .usdm import USDM
+        return USDM
     if name == "DeviceData":
         from .device_data import DeviceData
         return DeviceData

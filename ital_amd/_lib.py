@@ -380,6 +380,18 @@ KNN_SIGNATURES = {
 }
 
 
+#: the kernels of the USDM learner (graph Laplacian, LU without pivoting, shift, symmetric matvec), include/ital_usdm.h
+USDM_SIGNATURES = {
+    "ital_usdm_laplacian": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_double, c_void_p,
+                                    c_int64, c_void_p, c_void_p]),
+    "ital_lu_factor": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ital_lu_solve": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ital_usdm_shift": (c_int, [c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]),
+    "ital_symv_lower": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ital_symv_lower_workspace": (c_int64, [c_int64]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -403,7 +415,8 @@ def load(path=LIB_PATH):
             list(EVIDENCE_SIGNATURES.items()) + list(INGEST_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
             list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()) + list(INFLUENCE_SIGNATURES.items()) + \
-            list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
+            list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + \
+            list(USDM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

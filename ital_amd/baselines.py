@@ -4,9 +4,9 @@ TopscoringSampling, BorderlineSampling, BorderlineDiversitySampling, VarianceSam
 `use_correlations`), UncertaintySampling, EntropySampling (the orthant kernel of the ITAL scorer) and EMOC (the FP64
 MFMA covariance tiles of MCMI) -- reference ital/baseline_methods.py:12-155, :203-287, :338-381.  They exist so that the
 reference's comparison tables run through `ital_amd.harness` against the same GP; AdaptAL is a learner of its own
-(ital_amd/adapt_al.py), so are TCAL and RBMAL (ital_amd/competitors.py) and SUD (ital_amd/sud.py, on the neighbour lists of
-DeviceData.knn; not registered in the harness yet); USDM, which needs dense N x N solves on top of that structure, is out of
-scope.
+(ital_amd/adapt_al.py), so are TCAL and RBMAL (ital_amd/competitors.py), SUD (ital_amd/sud.py, on the neighbour lists of
+DeviceData.knn) and USDM (ital_amd/usdm.py: dense solves of the size of the unlabelled set on top of those lists); the last two
+are not registered in the harness yet.
 """
 import numpy as np
 import torch
