@@ -8,7 +8,7 @@ The arithmetic lives in hand-written HIP kernels (ital_amd/csrc, C ABI in includ
 from . import mvn_stream
 from .mvn_stream import GLOBAL as mvn_global_stream
 
-__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "SUD", "USDM", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode"]
+__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "SUD", "USDM", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode", "metrics"]
 
 
 def serving_mode():
@@ -50,4 +50,7 @@ def __getattr__(name):
     if name == "DeviceData":
         from .device_data import DeviceData
         return DeviceData
+    if name == "metrics":
+        import importlib
+        return importlib.import_module(".metrics", __name__)
     raise AttributeError(name)

@@ -1,7 +1,7 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
 include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_evidence_grad.h,
 include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h, include/ital_cosine.h,
-include/ital_reweigh.h and include/ital_knn.h).
+include/ital_reweigh.h, include/ital_knn.h and include/ital_rank.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -392,6 +392,17 @@ USDM_SIGNATURES = {
 }
 
 
+#: the complete ranking of a score vector and its AP / NDCG against relevance labels, declared in include/ital_rank.h
+RANK_TILE, RANK_EVAL_LEN = 2048, 6
+RANK_EVAL_FIELDS = ("ap", "ndcg", "n_pos", "n_neg", "n_unknown", "n_nan")       # the ITAL_RANK_* slots of the record, in order
+RANK_SIGNATURES = {
+    "ital_rank_desc": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "ital_rank_workspace": (ctypes.c_size_t, [c_int64]),
+    "ital_rank_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "ital_rank_eval_workspace": (ctypes.c_size_t, [c_int64]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -416,7 +427,7 @@ def load(path=LIB_PATH):
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
             list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()) + list(INFLUENCE_SIGNATURES.items()) + \
             list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + \
-            list(USDM_SIGNATURES.items()):
+            list(USDM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -1131,6 +1131,18 @@ class GaussianProcess(object):
         check(self._lib.ital_topk(_ptr(self.mu_all), n, 0, k, _ptr(vals), _ptr(idx), _ptr(self._topk_work), _stream()))
         return idx.cpu().numpy()
 
+    def rank_mean(self, k=None):
+        """The first k entries (None: all) of the complete ranking of the samples by predictive mean, in topk_mean's order,
+        sorted on the device (ital_rank_desc; metrics.rank): only the k indices asked for are downloaded.  Local operation
+        on the replicated means."""
+        from . import metrics
+        n = self.n_total
+        if k is not None and not (0 <= int(k) <= n):
+            raise ValueError("k outside 0..number of samples")
+        with torch.cuda.device(self.device):
+            order = metrics.rank(self.mu_all[:n])
+        return (order if k is None else order[: int(k)]).cpu().numpy()
+
     def predict_stored(self, ind=None, cov_mode=None):
         """Predictive mean / variance / covariance of samples of the data matrix (reference gp.py:203-232)."""
         if self.m == 0:
@@ -1204,10 +1216,13 @@ class GaussianProcess(object):
                                                             float(self.length_scale), _ptr(out[c0:c0 + c]), self.ldv, _stream()))
         return out[:, : self.n]
 
-    def predict(self, X, cov_mode=None):
+    def predict(self, X, cov_mode=None, on_device=False):
         """Predictive mean (and variance / full covariance) for external samples (reference gp.py:264-292).  Every rank
         computes it for all of X (the labelled-set state is replicated): no collective.  X: an array, or a torch tensor
-        (f16 / bf16 / f32 / f64, host or device) that ital_ingest_rows converts on the device."""
+        (f16 / bf16 / f32 / f64, host or device) that ital_ingest_rows converts on the device.  on_device (with cov_mode
+        None): the means stay where they were computed and come back as a float64 device tensor."""
+        if on_device and cov_mode is not None:
+            raise ValueError("on_device returns the means alone: cov_mode must be None")
         if self.m == 0:
             raise RuntimeError("the GP has not been fitted")
         if cov_mode not in (None, "diag", "full"):
@@ -1240,4 +1255,4 @@ class GaussianProcess(object):
                                            _ptr(Vt), ldvt, self.m, float(self.var), float(self.length_scale), _ptr(cov),
                                            ldvt, _stream()))
             return mean.cpu().numpy(), cov[:, :nt].cpu().numpy()
-        return mean.cpu().numpy()
+        return mean if on_device else mean.cpu().numpy()

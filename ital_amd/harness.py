@@ -3,7 +3,7 @@ registry, NDCG / AUC), `datasets.py` (the loaders whose data ship with the refer
 `run_experiment.py` (simulated relevance-feedback loop, AP / NDCG table), so that the reference's `configs/*.conf`
 run unchanged against `ital_amd.ITAL` / `ital_amd.MCMI_min` / `ital_amd.AdaptAL`:
 
-    python -m ital_amd.harness configs/iris.conf [--rounds=3 --repetitions=2 ...]
+    python -m ital_amd.harness configs/iris.conf [--rounds=3 --repetitions=2 ... --metrics=device]
 
 SURVEY.md section 8(f) row f2.  Semantics kept: value casting of every config entry (`utils.py:144-166`), the
 `import` directive (`:70-76`), `[EXPERIMENT]` overrides (`:79-80`), learner kwargs = `[METHOD_DEFAULTS]` + `[<method>]`
@@ -229,9 +229,13 @@ def simulate_retrieval_feedback(labels, ret, label_prob=0.8, mistake_prob=0.05):
     return fb
 
 
-def run_retrieval_experiment(config, dataset, learner, out=None, trace=None):
+def run_retrieval_experiment(config, dataset, learner, out=None, trace=None, metrics="host"):
     """Active retrieval rounds for every class and query (reference run_experiment.py:79-195).  `trace`, if a list,
-    receives (class, query, round, fetched batch, feedback)."""
+    receives (class, query, round, fetched batch, feedback).  metrics: "host", the reference's evaluation of every round
+    (download of the test scores, scikit-learn's average precision, ndcg() above), or "device", learner.evaluate() on the
+    test split (ital_amd/metrics.py)."""
+    if metrics not in ("host", "device"):
+        raise ValueError("metrics must be 'host' or 'device'")
     exp = "EXPERIMENT"
     out = sys.stdout if out is None else out
     classes = str(config.get(exp, "query_classes", fallback="")).split()
@@ -259,6 +263,9 @@ def run_retrieval_experiment(config, dataset, learner, out=None, trace=None):
             queries = np.random.choice(np.nonzero(np.asarray(relevance) > 0)[0], (reps, n_init), replace=False)
 
         def evaluate():
+            if metrics == "device":
+                res = learner.evaluate(test_relevance, dataset.X_test_norm)
+                return res["ap"], res["ndcg"]
             scores = np.asarray(learner.gp.predict(dataset.X_test_norm))
             return average_precision(test_relevance[known], scores[known]), ndcg(test_relevance, scores)
 
@@ -303,8 +310,9 @@ def main(argv=None):
         if arg.startswith("--") and "=" in arg:
             key, value = arg[2:].split("=", 1)
             overrides[key] = value
+    metrics = overrides.pop("metrics", "host")       # --metrics=device: every round is evaluated on the device
     config, dataset, learner = load_config(argv[0], "EXPERIMENT", overrides)
-    run_retrieval_experiment(config, dataset, learner)
+    run_retrieval_experiment(config, dataset, learner, metrics=metrics)
 
 
 if __name__ == "__main__":

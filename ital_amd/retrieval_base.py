@@ -262,14 +262,31 @@ class ActiveRetrievalBase(object):
         return self.gp.mean_host() if self._fitted else None
 
     def top_results(self, k=None):
-        """reference retrieval_base.py:64-75.  Up to ITAL_TOPK_MAX results are selected on the device (ital_topk, exact;
-        ties by descending index as the reversal of a stable ascending sort gives); the complete ranking (k = None) is
-        N-sized by definition and sorts the downloaded means on the host."""
+        """reference retrieval_base.py:64-75.  On a fitted learner the ranking is made on the device, exact, ties by descending
+        index as the reversal of a stable ascending sort gives: up to ITAL_TOPK_MAX results by a selection (ital_topk), more
+        of them and the complete ranking (k = None) by a sort (ital_rank_desc); only the indices returned are downloaded."""
         from ._lib import ITAL_TOPK_MAX
         if k is not None and self._fitted and 1 <= int(k) <= min(ITAL_TOPK_MAX, self._num_samples()):
             return self.gp.topk_mean(int(k))
+        if self._fitted and (k is None or int(k) > ITAL_TOPK_MAX):
+            return self.gp.rank_mean(None if k is None else min(int(k), self._num_samples()))
         ind = np.argsort(self.rel_mean, kind="stable")[::-1]
         return ind[:k] if k is not None else ind
+
+    def evaluate(self, relevance, X=None):
+        """Average precision and NDCG of the current model against `relevance` (+1 / -1 per sample, 0: unknown, left out),
+        computed on the device (metrics.evaluate: ranking, tie groups and sums; 48 bytes come back): the scores are the
+        predictive means of the stored samples, or, with `X`, those of external points (gp.predict on the device; relevance
+        then has one entry per row of X) -- what the reference's experiment loop computes on the host after every round
+        (run_experiment.py:154-168).  Returns {"ap", "ndcg", "n_pos", "n_neg", "n_unknown"}.  RuntimeError before any feedback;
+        ValueError when no sample is relevant or a score is NaN.  Local operation on the replicated state."""
+        from . import metrics
+        if not self._fitted:
+            raise RuntimeError("evaluate() needs a fitted model: call update() first")
+        import torch
+        with torch.cuda.device(self.gp.device):
+            scores = self.gp.mu_all[: self._num_samples()] if X is None else self.gp.predict(X, on_device=True)
+            return metrics.evaluate(scores, relevance)
 
     def get_unseen(self):
         """reference retrieval_base.py:78-87 (ascending sample indices, python ints)."""
