@@ -8,7 +8,7 @@ The arithmetic lives in hand-written HIP kernels (ital_amd/csrc, C ABI in includ
 from . import mvn_stream
 from .mvn_stream import GLOBAL as mvn_global_stream
 
-__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "SUD", "USDM", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "mvn_stream", "mvn_global_stream", "serving_mode", "metrics"]
+__all__ = ["ITAL", "MCMI_min", "AdaptAL", "TCAL", "RBMAL", "SUD", "USDM", "GaussianProcess", "ActiveRetrievalBase", "DeviceData", "prepare", "column_stats", "MinMax", "PCA", "Transform", "principal_axes", "mvn_stream", "mvn_global_stream", "serving_mode", "metrics"]
 
 
 def serving_mode():
@@ -50,6 +50,12 @@ def __getattr__(name):
     if name == "DeviceData":
         from .device_data import DeviceData
         return DeviceData
+    if name == "prepare":
+        import importlib
+        return importlib.import_module(".prepare", __name__)
+    if name in ("column_stats", "MinMax", "PCA", "Transform", "principal_axes"):
+        from . import prepare
+        return getattr(prepare, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

@@ -1,7 +1,7 @@
 """ctypes binding of libital_hip.so (the C ABI declared in include/ital_hip.h, include/ital_ctx.h, include/ital_dense.h,
 include/ital_adapt.h, include/ital_revoke.h, include/ital_rewhiten.h, include/ital_evidence.h, include/ital_evidence_grad.h,
 include/ital_loo_grad.h, include/ital_ingest.h, include/ital_rows.h, include/ital_compact.h, include/ital_cosine.h,
-include/ital_reweigh.h, include/ital_knn.h and include/ital_rank.h).
+include/ital_reweigh.h, include/ital_knn.h, include/ital_rank.h and include/ital_prepare.h).
 
 The product path has no CPU fallback: if the HIP library is missing this module raises at import.
 """
@@ -403,6 +403,23 @@ RANK_SIGNATURES = {
 }
 
 
+#: column statistics, min-max scaling, the centred scatter matrix and the projection of feature rows, include/ital_prepare.h
+PREPARE_STATS_UNIT, PREPARE_STATS_CAP, PREPARE_COV_UNIT, PREPARE_COV_CAP, PREPARE_MAX_K = 128, 1024, 512, 32, 512
+PREPARE_SIGNATURES = {
+    "ital_prepare_ranges": (c_int64, [c_int64, c_int, c_int]),
+    "ital_col_cov_cap": (c_int, [c_int]),
+    "ital_col_stats": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t,
+                               c_void_p]),
+    "ital_col_stats_workspace": (ctypes.c_size_t, [c_int64, c_int]),
+    "ital_scale_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ital_col_cov": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, ctypes.c_size_t,
+                             c_void_p]),
+    "ital_col_cov_workspace": (ctypes.c_size_t, [c_int64, c_int]),
+    "ital_project_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                  c_int, c_void_p]),
+}
+
+
 class ItalHipError(RuntimeError):
     pass
 
@@ -427,7 +444,7 @@ def load(path=LIB_PATH):
             list(COMPACT_SIGNATURES.items()) + list(EVIDENCE_GRAD_SIGNATURES.items()) + list(LOO_GRAD_SIGNATURES.items()) + \
             list(CTX_LIVE_SIGNATURES.items()) + list(COSINE_SIGNATURES.items()) + list(INFLUENCE_SIGNATURES.items()) + \
             list(CTX_AUDIT_SIGNATURES.items()) + list(REWEIGH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + \
-            list(USDM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
+            list(USDM_SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PREPARE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what the headers declare
         fn.restype = res
         fn.argtypes = args

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libital_hip.so")
-SOURCES = ["api.hip", "rbf.hip", "chol.hip", "score.hip", "select.hip", "mcmi.hip", "score_generic.hip", "gen_pipeline.hip", "topk.hip", "exchange.hip", "round.hip", "ctx.hip", "ctx_live.hip", "dense.hip", "adapt.hip", "revoke.hip", "rewhiten.hip", "evidence.hip", "evidence_grad.hip", "loo_grad.hip", "ingest.hip", "rows.hip", "compact.hip", "cosine.hip", "influence.hip", "ctx_audit.hip", "reweigh.hip", "knn.hip", "usdm.hip", "rank.hip",
+SOURCES = ["api.hip", "rbf.hip", "chol.hip", "score.hip", "select.hip", "mcmi.hip", "score_generic.hip", "gen_pipeline.hip", "topk.hip", "exchange.hip", "round.hip", "ctx.hip", "ctx_live.hip", "dense.hip", "adapt.hip", "revoke.hip", "rewhiten.hip", "evidence.hip", "evidence_grad.hip", "loo_grad.hip", "ingest.hip", "rows.hip", "compact.hip", "cosine.hip", "influence.hip", "ctx_audit.hip", "reweigh.hip", "knn.hip", "usdm.hip", "rank.hip", "prepare.hip",
            "mvn_stream.cpp", "np_legacy.cpp"]    # .cpp: host-only translation units (no HIP), also built by tools/asan_host.sh
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXTRA = os.environ.get("ITAL_HIPCC_EXTRA", "").split()          # added to every .hip compile (kernel-variant experiments)
